@@ -199,6 +199,25 @@ def _weak_leg(args, dev, world, make_engine, first_comm=None):
             "envs_per_gpu": args.envs, "steps": k, "ms_per_step": round(float(t.item()) / k * 1e3, 4)}
 
 
+def dump_outputs(out_dir, trainer, data, train_info):
+    """--dump-outputs: what a caller of the timed path holds after its last step - the update's train_info, the new
+    weights of both towers, the ValueNorm state, and the rollout + GAE arrays the update consumed - one float32 /
+    float64 .npy per name (about 10 MB at the default shape)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"train_" + k: np.asarray([v], dtype=np.float64) for k, v in sorted(train_info.items())}
+    mod = trainer.algo_module
+    for name in ("policy", "critic"):
+        arrays[name + "_theta"] = mod.models[name].theta
+    arrays["value_normalizer_state"] = mod.get_critic_value_normalizer().state
+    for name in ("actions", "action_log_probs", "value_preds", "rewards", "returns"):
+        arrays["buffer_" + name] = getattr(data, name)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -227,7 +246,13 @@ def main():
                     help="world > 1: skip the short weak-scaling run (4096 envs per rank) reported next to the strong number")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the few untimed iterations of BASELINE.json's other single-GPU configs (other_configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (train_info, both towers' weights, "
+                         "the ValueNorm state, the rollout buffer's actions / log-probs / values / rewards / returns) as "
+                         "DIR/<name>.npy (rank 0); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: re-launch as N ranks, one process per GPU (torch.distributed.run is what
@@ -318,6 +343,14 @@ def main():
     barrier()
     t0 = time.perf_counter()
     info = {}
+    last_train_info = []
+    orig_train = trainer.train
+
+    def kept_train(*a, **k):  # the last timed step's train_info (lazy: read only after the timed region)
+        ti = orig_train(*a, **k)
+        last_train_info.append(ti)
+        return ti
+
     for i in range(args.steps):
         if i in block_edges:
             e = torch.cuda.Event(enable_timing=True)
@@ -326,6 +359,8 @@ def main():
         sampled = i % ev_stride == 0
         trainer.profile_events = tower_events if sampled else None
         buf.data.compute_returns = timed_compute_returns if sampled else orig_cr
+        if args.dump_outputs and i == args.steps - 1:
+            trainer.train = kept_train
         drv.episode = args.warmup + i
         drv._inner_loop()
     e = torch.cuda.Event(enable_timing=True)
@@ -333,8 +368,12 @@ def main():
     block_events.append(e)
     trainer.profile_events = None
     buf.data.compute_returns = orig_cr
+    if args.dump_outputs:
+        del trainer.train  # back to the class's method
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before the untimed iteration below moves the weights and the buffer on
+        dump_outputs(args.dump_outputs, trainer, buf.data, last_train_info[-1])
     block_ms = [block_events[k].elapsed_time(block_events[k + 1]) / max(block_edges[k + 1] - block_edges[k], 1)
                 for k in range(len(block_events) - 1)]
     if world > 1:

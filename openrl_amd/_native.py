@@ -282,6 +282,7 @@ _SIGNATURES = {
 }
 
 _lib: Optional[C.CDLL] = None
+_experiments_lib: Optional[C.CDLL] = None
 
 
 def exported_symbols():
@@ -302,7 +303,23 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     elif build_if_missing and _b.have_hipcc() and not os.environ.get("ORL_KEEP_BUILD"):
         # (ORL_KEEP_BUILD=1: measurement tools that load a deliberately different build, e.g. --prof)
         _b.build()  # no-op when the source digest matches the stamp; rebuilds a stale shared object
-    lib = C.CDLL(LIB_PATH)
+    _lib = _open(LIB_PATH)
+    return _lib
+
+
+def load_experiments() -> C.CDLL:
+    """The ORL_BUILD_EXPERIMENTS build of the same sources (built or rebuilt as needed), NOT made the current library:
+    its tests swap it in for their own duration (tests/conftest.py).  Raises if unavailable."""
+    global _experiments_lib
+    if _experiments_lib is None:
+        from .csrc import build as _b
+
+        _experiments_lib = _open(_b.build(experiments=True))
+    return _experiments_lib
+
+
+def _open(path: str) -> C.CDLL:
+    lib = C.CDLL(path)
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale -> loud failure
         fn.restype = res
@@ -310,12 +327,11 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     # a stale build can export the same names with another struct layout: refuse it instead of corrupting memory
     if lib.orl_version() != ORL_VERSION:
         raise NativeError("%s is version %d, the bindings are %d - rebuild with `python -m openrl_amd.csrc.build "
-                          "--force`" % (LIB_PATH, lib.orl_version(), ORL_VERSION))
+                          "--force`" % (path, lib.orl_version(), ORL_VERSION))
     for which, st in enumerate(_ABI_STRUCTS):
         if lib.orl_abi_struct_size(which) != C.sizeof(st):
             raise NativeError("ABI mismatch: %s is %d bytes in %s, %d in the bindings" %
-                              (st.__name__, lib.orl_abi_struct_size(which), LIB_PATH, C.sizeof(st)))
-    _lib = lib
+                              (st.__name__, lib.orl_abi_struct_size(which), path, C.sizeof(st)))
     return lib
 
 

@@ -20,6 +20,9 @@ HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.joi
 FAST_MATH = {"orl_ppo.hip", "orl_rnn.hip", "orl_rnn_rollout.hip", "orl_mpe.hip", "orl_act.hip", "orl_gen_rollout.hip"}  # NOT orl_gen.hip: torch-like IEEE arithmetic there
 LIB = os.path.join(HERE, "liborl_hip.so")
 STAMP = os.path.join(HERE, ".liborl_hip.stamp")
+# the same sources with -DORL_BUILD_EXPERIMENTS=1: the comparison kernels that lost their A/B, for their tests only
+EXPERIMENTS_LIB = os.path.join(HERE, "liborl_hip_experiments.so")
+EXPERIMENTS_STAMP = os.path.join(HERE, ".liborl_hip_experiments.stamp")
 ARCH = "gfx950"
 
 
@@ -44,16 +47,20 @@ def _digest() -> str:
     return h.hexdigest()
 
 
-def build(force: bool = False, verbose: bool = False, prof: bool = False) -> str:
+def build(force: bool = False, verbose: bool = False, prof: bool = False, experiments: bool = False) -> str:
     srcs = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     # build-time A/B switches for kernel experiments (e.g. ORL_BUILD_DEFS="-DORL_TOWER_ILV"); never read at run time
     extra = os.environ.get("ORL_BUILD_DEFS", "").split()
+    lib_path, stamp_path, obj_tag = LIB, STAMP, ""
+    if experiments:
+        extra = extra + ["-DORL_BUILD_EXPERIMENTS=1"]
+        lib_path, stamp_path, obj_tag = EXPERIMENTS_LIB, EXPERIMENTS_STAMP, ".experiments"
     compress = os.environ.get("ORL_NO_OFFLOAD_COMPRESS", "") == ""
     dig = _digest() + ("-prof" if prof else "") + ("-oc" if compress else "") + "".join(extra)  # a library built with other switches is not up to date
-    if not force and os.path.exists(LIB) and os.path.exists(STAMP):
-        with open(STAMP) as fh:
+    if not force and os.path.exists(lib_path) and os.path.exists(stamp_path):
+        with open(stamp_path) as fh:
             if fh.read().strip() == dig:
-                return LIB
+                return lib_path
     # Per-source flags: the update and rollout kernels (towers, recurrent, act) are built with -ffast-math -
     # reassociation and 1-ulp hardware reciprocal / rsqrt / exp / sin / cos instead of the IEEE sequences (+5 % on
     # the bench iteration, every parity test unchanged); the buffer kernels are NOT (the GAE scan is bit-exact with
@@ -67,7 +74,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False) -> str
     if prof:  # phase-timing build of the tower kernels (orl_debug_prof); never the shipped configuration
         base.append("-DORL_PROF")
     def compile_one(src):
-        obj = os.path.splitext(src)[0] + ".o"
+        obj = os.path.splitext(src)[0] + obj_tag + ".o"
         cmd = base + (["-ffast-math"] if os.path.basename(src) in FAST_MATH else []) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
@@ -81,7 +88,7 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False) -> str
 
     with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as pool:
         objs = list(pool.map(compile_one, srcs))
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
+    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib_path] + objs
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     res = subprocess.run(cmd, capture_output=True, text=True)
@@ -90,10 +97,11 @@ def build(force: bool = False, verbose: bool = False, prof: bool = False) -> str
             os.remove(obj)
     if res.returncode != 0:
         raise RuntimeError("hipcc (link) failed:\n" + res.stdout + res.stderr)
-    with open(STAMP, "w") as fh:
+    with open(stamp_path, "w") as fh:
         fh.write(dig)
-    return LIB
+    return lib_path
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv or "--prof" in sys.argv, verbose=True, prof="--prof" in sys.argv))
+    print(build(force="--force" in sys.argv or "--prof" in sys.argv, verbose=True, prof="--prof" in sys.argv,
+                experiments="--experiments" in sys.argv))

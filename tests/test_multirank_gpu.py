@@ -29,10 +29,15 @@ def _run(args, timeout=900, env=None, nproc=2):
     return res, res.stdout + res.stderr
 
 
-# (mode, ranks, extra): beyond 2 ranks the sum is no longer commutative-trivial - rank-ordered summation, the 8-source
+# At most 6 processes may have the GPU open at once: the pytest process, torch.distributed.run's launcher (it initialises
+# HIP) and the ranks - so no case runs more than MAX_RANKS ranks.
+MAX_RANKS = 4
+
+
+# (mode, ranks, extra): beyond 2 ranks the sum is no longer commutative-trivial - rank-ordered summation, the per-world
 # inbox stride and shard_range remainders ("odd": 24 * G + G - 1 envs) are all live
 @pytest.mark.parametrize("mode,nproc,extra", [("mlp", 2, []), ("rnn", 2, []), ("gen", 2, []), ("genrnn", 2, []),
-                                              ("mlp", 3, ["odd"]), ("mlp", 4, []), ("mlp", 8, ["odd"]),
+                                              ("mlp", 3, ["odd"]), ("mlp", 4, []), ("mlp", MAX_RANKS, ["odd"]),
                                               ("rnn", 4, ["odd"]), ("gen", 3, ["odd"]), ("genrnn", 4, [])])
 def test_ranks_equal_one_rank_on_the_concatenated_batch(mode, nproc, extra):
     res, out = _run([os.path.join(ROOT, "tests", "multirank_equiv.py"), mode] + extra, nproc=nproc)
@@ -42,10 +47,10 @@ def test_ranks_equal_one_rank_on_the_concatenated_batch(mode, nproc, extra):
     assert res.returncode == 0, out[-3000:]
 
 
-@pytest.mark.parametrize("nproc", [2, 4, 8])
+@pytest.mark.parametrize("nproc", [2, 3, MAX_RANKS])
 def test_one_shot_p2p_allreduce_is_the_rank_ordered_sum_bitwise(nproc):
     """orl_allreduce_small (hipIpc-mapped peer inboxes, 8-byte {value, sequence} granules, rank-ordered sum) vs an
-    all_gather + explicit rank-order fp32 sum over 10 back-to-back collectives of sizes 1 .. 20 000 floats; 2 / 4 / 8
+    all_gather + explicit rank-order fp32 sum over 10 back-to-back collectives of sizes 1 .. 20 000 floats; 2 / 3 / 4
     processes on cuda:0."""
     res, out = _run([os.path.join(ROOT, "tests", "multirank_equiv.py"), "comm"], nproc=nproc)
     assert "COMM_OK" in out, out[-3000:]

@@ -269,8 +269,6 @@ def test_one_launch_optimiser_step_equals_the_two_launch_one_bit_for_bit(case, p
     ``step`` = orl_ppo_step (round 6: two designated optimiser workgroups wait for the write-through column sums behind a
     ticket word - same time as two launches, so not the default); ``fused`` = orl_ppo_reduce_apply (round 5's ticketed form behind cache fences, a
     comparison kernel)."""
-    if case == "train_cfg2_full" and (perm_mode, turn_on) != ("device", True):
-        pytest.skip("the full-size case runs once")
     g = H.load_golden(case)
     outs = []
     for step in (one_launch, "two_launch"):
@@ -476,7 +474,7 @@ def test_full_size_update_other_baseline_shapes_match_reference_golden(case, bra
     _assert_golden_outputs(g, module, info)
 
 
-@pytest.mark.skipif(not H.experiments_built(), reason="the fp32-MFMA tower pair is a comparison kernel: needs an ORL_BUILD_EXPERIMENTS library")
+@pytest.mark.experiments  # the fp32-MFMA tower pair is a comparison kernel
 def test_split_bf16_gemms_are_as_accurate_as_the_fp32_mfma_at_full_size():
     """The tower update's GEMMs as exact three-term bf16 splits (default) vs the fp32 MFMA (``amd_tower_gemm=fp32``,
     ``orl_ppo_hparams.reserved & 4``): one full-batch update at BASELINE configs[1]'s size (524 288 rows), clipped
