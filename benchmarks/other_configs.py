@@ -5,7 +5,8 @@
 
 configs[2] at its SHAPE on the synthetic env (1024 envs x 200, obs 17, Box(6); MuJoCo is not available offline),
 configs[3] end to end (device MPE simple_spread, 2048 envs x 3 agents x 25, GRU, chunks of 2) and configs[4]'s env end
-to end (device tic-tac-toe, 4096 envs x 200, Discrete(9) + legal-move masks, random opponent).  Reference defaults
+to end (device tic-tac-toe, 4096 envs x 200, Discrete(9) + legal-move masks, random opponent), and Pendulum-v1 end to end
+(device env, 4096 envs x 200, Box(1), Gaussian head).  Reference defaults
 otherwise (ppo_epoch 10, num_mini_batch 1, hidden 64).  ``dominant_kernel_ms`` = HIP-event time of one forward +
 backward launch of the update (tower pair / recurrent row pair), averaged over the timed iterations."""
 import json
@@ -32,6 +33,10 @@ CONFIGS = [
     dict(name="non-default tower: configs[1]'s shape with hidden_size 128 (cross-layer fused general towers)",
          env="SyntheticFixedStep-v0", envs=4096, T=128, agents=1, env_kw=dict(obs_dim=4, episode_limit=200),
          argv=["--hidden_size", "128"]),
+    # not a BASELINE config: the Gaussian head on a real control task - Pendulum-v1's dynamics in the chain rollout kernel
+    # (csrc/orl_env.h + orl_rollout2.h), default towers
+    dict(name="Pendulum-v1, PPO, 4096 envs x 200, obs 3, Box(1), device env, fused rollout", env="Pendulum-v1", envs=4096,
+         T=200, agents=1, env_kw={}, argv=[]),
 ]
 
 

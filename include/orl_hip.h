@@ -418,6 +418,10 @@ int orl_minibatch_moments(const float* records, int rec_width, int ret_col, cons
 #define ORL_ENV_CARTPOLE 1 /* CartPole-v1 dynamics (gymnasium classic_control cartpole.py) */
 #define ORL_ENV_TTT 2      /* tic-tac-toe vs a uniformly random opponent (orl_ttt_*): obs 18, Discrete(9), legal-move masks */
 #define ORL_ENV_TTT_POOL 3 /* the same game, the opponent of env group g is policy g of a pool (orl_rollout_args.opp_*) */
+/* ORL_ENV_MPE_SPREAD 4: below (orl_rnn_rollout_fused) */
+#define ORL_ENV_PENDULUM 5 /* Pendulum-v1 dynamics (gymnasium classic_control pendulum.py, fp32, th wrapped to [-pi, pi) every
+                            * step): obs 3 (cos th, sin th, thdot), Box(-2, 2, (1,)) float actions, never terminates.  Fused
+                            * rollout: the chain kernel only (Gaussian head, n_out 1, obs_dim 3; opp_reserved 1 is rejected) */
 
 typedef struct orl_rollout_args {
   orl_buffer_ptrs buf;
@@ -435,7 +439,7 @@ typedef struct orl_rollout_args {
   const float* opp_thetas; /* parameters of policy g at opp_thetas + g*opp_theta_stride */
   int64_t opp_theta_stride;
   int32_t opp_group_rows;  /* envs [g*opp_group_rows, ...) play policy g; a multiple of 16 */
-  int32_t opp_reserved;    /* ORL_ENV_SYNTH / ORL_ENV_CARTPOLE / ORL_ENV_TTT: 0 = the round-6 chain rollout (policy-only step chain, the
+  int32_t opp_reserved;    /* ORL_ENV_SYNTH / ORL_ENV_CARTPOLE / ORL_ENV_TTT / ORL_ENV_PENDULUM: 0 = the round-6 chain rollout (policy-only step chain, the
                             * critic on background waves of the same launch), 1 = the round-5 kernel (both towers in the
                             * step loop).  Ignored by the tic-tac-toe POOL envs (always the round-5 kernel). */
   uint64_t opp_seed;       /* Philox seed of the opponents' sampling; counter = (env, opp_rng_step0 + t) */

@@ -1,7 +1,7 @@
 // orl_act.hip - rollout side of the hot path for gfx950:
 //   orl_act_step      : K1-K4 fused policy + value forward and action sampling for B rows
 //   orl_rollout_fused : T steps of {forward, sample, env.step, buffer insert} in ONE launch for
-//                       device-resident batched envs (synthetic fixed-step env, CartPole-v1)
+//                       device-resident batched envs (synthetic fixed-step env, CartPole-v1, Pendulum-v1)
 //   orl_env_reset     : initial env state + first observation
 //
 // Geometry: one workgroup owns one 16-row tile (fp32 MFMA 16x16x4, see orl_mlp.h).  orl_act_step uses 2
@@ -159,6 +159,12 @@ __global__ __launch_bounds__(256) void env_reset_kernel(float* __restrict__ env_
       for (int k = 0; k < 4; ++k)
         if (4 * b + k < D) obs0[(size_t)n * D + 4 * b + k] = o[k];
     }
+  } else if (ENV == ORL_ENV_PENDULUM) {
+    float* st = env_state + (size_t)n * PENDULUM_STATE_W;
+    float s[2];
+    pendulum_reset(seed, (uint32_t)n, 0u, s);
+    pendulum_obs(s, obs0 + (size_t)n * 3);
+    st[0] = s[0]; st[1] = s[1]; st[2] = 0.f; st[3] = 0.f;
   } else {
     float* st = env_state + (size_t)n * CARTPOLE_STATE_W;
     float s[4];
@@ -940,7 +946,7 @@ __global__ __launch_bounds__(256) void env_step_kernel(float* __restrict__ env_s
   if (tg_dev) tg += (uint64_t)*tg_dev;  // hipGraph replays: the host part is frozen, the device part advances
   float r;
   bool d;
-  env_step_one<ENV>(env_state, ep_stats, n, D, seed, episode_limit, tg, ENV == ORL_ENV_SYNTH ? 0 : (int)actions[(size_t)n * a_w],
+  env_step_one<ENV>(env_state, ep_stats, n, D, seed, episode_limit, tg, ENV == ORL_ENV_SYNTH ? 0.f : actions[(size_t)n * a_w],
                     obs + (size_t)n * D, r, d);
   rew[n] = r;
   done[n] = d ? 1 : 0;
@@ -1216,6 +1222,7 @@ int orl_evaluate_actions(const orl_net_desc* pnet, const float* ptheta, const or
 int orl_env_state_width(int env_kind) {
   if (env_kind == ORL_ENV_SYNTH) return SYNTH_STATE_W;
   if (env_kind == ORL_ENV_CARTPOLE) return CARTPOLE_STATE_W;
+  if (env_kind == ORL_ENV_PENDULUM) return PENDULUM_STATE_W;
   return fail(ORL_E_INVALID, "orl_env_state_width: unknown env kind %d", env_kind);
 }
 
@@ -1229,6 +1236,10 @@ int orl_env_reset(int env_kind, float* env_state, float* ep_stats, float* obs0, 
   } else if (env_kind == ORL_ENV_CARTPOLE) {
     ORL_REQUIRE(obs_dim == 4, "orl_env_reset: CartPole obs_dim must be 4");
     hipLaunchKernelGGL((env_reset_kernel<ORL_ENV_CARTPOLE>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                       env_state, ep_stats, obs0, N, obs_dim, env_seed, episode_limit);
+  } else if (env_kind == ORL_ENV_PENDULUM) {
+    ORL_REQUIRE(obs_dim == 3, "orl_env_reset: Pendulum obs_dim must be 3");
+    hipLaunchKernelGGL((env_reset_kernel<ORL_ENV_PENDULUM>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        env_state, ep_stats, obs0, N, obs_dim, env_seed, episode_limit);
   } else {
     return fail(ORL_E_INVALID, "orl_env_reset: unknown env kind %d", env_kind);
@@ -1256,6 +1267,13 @@ int orl_env_step_dev(int env_kind, float* env_state, float* ep_stats, const floa
   } else if (env_kind == ORL_ENV_CARTPOLE) {
     ORL_REQUIRE(actions && action_width >= 1 && obs_dim == 4, "orl_env_step: CartPole needs actions and 4-d obs");
     hipLaunchKernelGGL((env_step_kernel<ORL_ENV_CARTPOLE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, env_state,
+                       ep_stats, actions, action_width, obs, rewards, dones, N, obs_dim, env_seed, episode_limit,
+                       global_step, (const long long*)global_step_dev);
+  } else if (env_kind == ORL_ENV_PENDULUM) {
+    ORL_REQUIRE(actions && action_width == 1 && obs_dim == 3,
+                "orl_env_step: Pendulum needs float actions of width 1 and 3-d obs (got width %d, obs_dim %d)", action_width,
+                obs_dim);
+    hipLaunchKernelGGL((env_step_kernel<ORL_ENV_PENDULUM>), dim3(grid), dim3(256), 0, (hipStream_t)stream, env_state,
                        ep_stats, actions, action_width, obs, rewards, dones, N, obs_dim, env_seed, episode_limit,
                        global_step, (const long long*)global_step_dev);
   } else {
@@ -1314,6 +1332,16 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
   if (args->env_kind == ORL_ENV_CARTPOLE)
     ORL_REQUIRE(pnet->head_kind == ORL_HEAD_CATEGORICAL && pnet->n_out == 2 && b.Dp == 4,
                 "orl_rollout_fused: CartPole needs Discrete(2) and 4-d obs");
+  const bool pend = args->env_kind == ORL_ENV_PENDULUM;
+  if (pend) {
+    ORL_REQUIRE(pnet->head_kind == ORL_HEAD_GAUSSIAN && pnet->n_out == 1 && b.Dp == 3,
+                "orl_rollout_fused: Pendulum needs a Gaussian head with n_out 1 and 3-d obs (got head %d, n_out %d, obs %d)",
+                pnet->head_kind, pnet->n_out, b.Dp);
+    // the round-5 lock-step kernel has no Pendulum instance (only the chain kernel steps it)
+    ORL_REQUIRE(args->opp_reserved != 1,
+                "orl_rollout_fused: Pendulum runs on the chain kernel only - opp_reserved = 1 (amd_rollout_kernel=lockstep) "
+                "selects the round-5 lock-step kernel, which is not built for it");
+  }
   const bool pool = args->env_kind == ORL_ENV_TTT_POOL;
   const bool perk = pool && args->opp_per_reset != 0;  // per-env opponents, re-drawn in-kernel at every auto-reset
   if (pool)
@@ -1347,7 +1375,7 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
   RolloutArgs A;
   A.pnet = *pnet; A.cnet = *cnet; A.ptheta = ptheta; A.ctheta = ctheta; A.r = *args; A.next_value = next_value;
   const int grid = (b.N + TILE_B - 1) / TILE_B;
-  // Round 6: the synthetic env and CartPole roll out on the chain kernel (orl_rollout2.h: policy-only step chain, the critic on
+  // Round 6: the synthetic env, CartPole, tic-tac-toe (random opponent) and Pendulum roll out on the chain kernel (orl_rollout2.h: policy-only step chain, the critic on
   // background waves of the same launch).  args.opp_reserved = 1 keeps the round-5 lock-step kernel (policy + critic in the
   // step loop) - the A/B switch of tests and benchmarks.
   const size_t lds2 = (size_t)ro2_lds(TowerLds(pnet->obs_dim, pnet->n_out, pnet->head_kind == ORL_HEAD_GAUSSIAN, false, pnet->n_out > 2,
@@ -1356,7 +1384,10 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
                       sizeof(float);
   // (the widest towers - observations of ~60 columns with 16 outputs - do not fit the chain kernel's rings beside both tower
   // images: they keep the round-5 kernel)
-  if ((args->env_kind == ORL_ENV_SYNTH || args->env_kind == ORL_ENV_CARTPOLE || args->env_kind == ORL_ENV_TTT) &&
+  // (Pendulum's towers - obs 3, one output - are far below the LDS limit: the fallback below never has to take it)
+  if (pend && lds2 > 160 * 1024)
+    return fail(ORL_E_INVALID, "orl_rollout_fused: Pendulum's chain kernel needs %zu B of LDS (> 160 KiB)", lds2);
+  if ((args->env_kind == ORL_ENV_SYNTH || args->env_kind == ORL_ENV_CARTPOLE || args->env_kind == ORL_ENV_TTT || pend) &&
       args->opp_reserved != 1 && lds2 <= 160 * 1024) {
 #define ORL_RO2_LAUNCH3(NO, HD, EV, KS)                                                                               \
   do {                                                                                                               \
@@ -1367,6 +1398,8 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
   } while (0)
     if (args->env_kind == ORL_ENV_CARTPOLE) {
       ORL_RO2_LAUNCH3(2, ORL_HEAD_CATEGORICAL, ORL_ENV_CARTPOLE, 1);
+    } else if (pend) {
+      ORL_RO2_LAUNCH3(2, ORL_HEAD_GAUSSIAN, ORL_ENV_PENDULUM, 1);  // narrow Gaussian head, fc1's single k-step at compile time
     } else if (args->env_kind == ORL_ENV_TTT) {
       ORL_RO2_LAUNCH3(16, ORL_HEAD_CATEGORICAL, ORL_ENV_TTT, 0);  // the random opponent (the pool variants keep the round-5 kernel)
     } else if (twp.DP == 4 && pnet->head_kind == ORL_HEAD_CATEGORICAL && pnet->n_out <= 2) {

@@ -1,6 +1,6 @@
-// orl_env.h - the device-resident single-agent envs (synthetic fixed-step env of SURVEY.md section 8d, CartPole-v1) as
-// per-env device functions, shared by the fused rollout kernels (orl_act.hip: default towers, orl_gen_fused.hip: general
-// towers) and the stand-alone env kernels: one definition, so every route steps an env with the same arithmetic and the
+// orl_env.h - the device-resident single-agent envs (synthetic fixed-step env of SURVEY.md section 8d, CartPole-v1,
+// Pendulum-v1) as per-env device functions, shared by the fused rollout kernels (orl_act.hip: default towers,
+// orl_gen_fused.hip: general towers) and the stand-alone env kernels: one definition, so every route steps an env with the same arithmetic and the
 // same Philox streams.  Not part of the C ABI.
 #pragma once
 #include "orl_common.h"
@@ -13,6 +13,7 @@ namespace orl {
 // --------------------------------------------------------------------------------------------------
 constexpr int SYNTH_STATE_W = 4;     // {steps_in_episode, -, -, -}
 constexpr int CARTPOLE_STATE_W = 8;  // {x, x_dot, theta, theta_dot, steps_in_episode, episodes, -, -}
+constexpr int PENDULUM_STATE_W = 4;  // {th, thdot, steps_in_episode, episodes}
 
 // synthetic obs component block b (4 normals) for (env, global time t)
 __device__ inline void synth_obs_block(uint64_t seed, uint32_t env, uint64_t t, uint32_t b, float (&o)[4]) {
@@ -68,12 +69,69 @@ __device__ inline bool cartpole_step(float (&s)[4], int action) {
 }
 
 
+// Pendulum-v1 (gymnasium/envs/classic_control/pendulum.py: max_speed 8, max_torque 2, dt 0.05, g 10, m 1, l 1) in fp32.
+// Reset: th ~ U(-pi, pi), thdot ~ U(-1, 1) from the engine's own Philox stream keyed (seed, env, episode) - not gymnasium's
+// np_random, as for CartPole.
+//
+// Deviation (fp32): gymnasium keeps th unwrapped in float64.  Here th is wrapped back to [-pi, pi) after every step
+// (pendulum_wrap: one conditional +-2 pi; |th + dt thdot| <= pi + 0.4 never needs more).  In real arithmetic nothing changes
+// - cos, sin and angle_normalize are 2 pi-periodic - but an unwrapped fp32 th after a few turns (|th| up to ~80 rad in an
+// episode) loses ~6 bits of the dt * thdot increment and pushes sinf / cosf (-ffast-math) into their weak range reduction.
+constexpr float PEND_PI = 3.14159265358979323846f, PEND_2PI = 6.28318530717958647692f;
+__device__ inline void pendulum_reset(uint64_t seed, uint32_t env, uint32_t episode, float (&s)[2]) {
+  const u4 r = philox4x32_10(seed, env, 0x9E4D0000u, episode, 0u);
+  s[0] = fmaf(u01(r.x), PEND_2PI, -PEND_PI);
+  s[1] = fmaf(u01(r.y), 2.0f, -1.0f);
+}
+// angle_normalize(x) = ((x + pi) mod 2 pi) - pi with Python's FLOORED modulo: fmodf truncates toward zero, so a negative
+// remainder takes + 2 pi
+__device__ inline float pendulum_angle_normalize(float x) {
+  float r = fmodf(x + PEND_PI, PEND_2PI);
+  r = r < 0.f ? r + PEND_2PI : r;
+  return r - PEND_PI;
+}
+__device__ inline float pendulum_wrap(float th) {
+  return th >= PEND_PI ? th - PEND_2PI : (th < -PEND_PI ? th + PEND_2PI : th);
+}
+// The step in two halves, as CartPole's: the action-independent terms (pendulum_pre: the gravity term 3 g / (2 l) sin th and
+// the cost's angle_normalize(th)^2 + 0.1 thdot^2) and the rest (pendulum_post: the torque clip, the action's cost, the
+// integration, the speed clip, the wrap and the new angle's cos / sin).  Explicit fmaf: every route runs exactly these
+// operations whatever the compiler would contract.
+struct PendulumPre {
+  float grav, cost0;  // 15 sin th, angle_normalize(th)^2 + 0.1 thdot^2
+};
+__device__ inline PendulumPre pendulum_pre(float th, float thdot) {
+  const float an = pendulum_angle_normalize(th);
+  PendulumPre p;
+  p.grav = 15.0f * sinf(th);
+  p.cost0 = fmaf(0.1f * thdot, thdot, an * an);
+  return p;
+}
+// s = {th, thdot} in / out; returns the reward, writes the observation (cos th', sin th', thdot')
+__device__ inline float pendulum_post(const PendulumPre& p, float (&s)[2], float action, float (&obs)[3]) {
+  const float u = fminf(fmaxf(action, -2.0f), 2.0f);
+  const float cost = fmaf(0.001f * u, u, p.cost0);
+  const float acc = fmaf(3.0f, u, p.grav);
+  const float thdot = fminf(fmaxf(fmaf(acc, 0.05f, s[1]), -8.0f), 8.0f);
+  const float th = pendulum_wrap(fmaf(thdot, 0.05f, s[0]));
+  float sn, cs;
+  sincosf(th, &sn, &cs);
+  s[0] = th; s[1] = thdot;
+  obs[0] = cs; obs[1] = sn; obs[2] = thdot;
+  return -cost;
+}
+__device__ inline void pendulum_obs(const float (&s)[2], float* __restrict__ obs) {
+  float sn, cs;
+  sincosf(s[0], &sn, &cs);
+  obs[0] = cs; obs[1] = sn; obs[2] = s[1];
+}
+
 // One env.step of env `n` at global time `tg` on the env's state row `st` / episode statistics `e` (register or memory
 // copies): writes the next observation to obs_out[0..D), returns the reward and whether the episode ended.  The one
 // definition of the envs' arithmetic: every route steps through it.
 template <int ENV>
 __device__ inline void env_step_state(float* __restrict__ st, float* __restrict__ e, int n, int D, uint64_t seed,
-                                      int episode_limit, uint64_t tg, int action, float* __restrict__ obs_out, float& r,
+                                      int episode_limit, uint64_t tg, float action, float* __restrict__ obs_out, float& r,
                                       bool& d) {
   if (ENV == ORL_ENV_SYNTH) {
     r = synth_reward(seed, (uint32_t)n, tg);
@@ -86,9 +144,24 @@ __device__ inline void env_step_state(float* __restrict__ st, float* __restrict_
       for (int k = 0; k < 4; ++k)
         if (4 * b + k < D) obs_out[4 * b + k] = o[k];
     }
+  } else if (ENV == ORL_ENV_PENDULUM) {
+    float s[2] = {st[0], st[1]};
+    const PendulumPre p = pendulum_pre(s[0], s[1]);
+    float o[3];
+    r = pendulum_post(p, s, action, o);
+    const float steps = st[2] + 1.f;
+    d = steps >= (float)episode_limit;  // never terminates: truncation only (done = terminated or truncated, no bootstrap)
+    st[2] = d ? 0.f : steps;
+    if (d) {
+      st[3] += 1.f;
+      pendulum_reset(seed, (uint32_t)n, (uint32_t)st[3], s);  // auto-reset: the first observation of the next episode
+      pendulum_obs(s, o);
+    }
+    st[0] = s[0]; st[1] = s[1];
+    for (int k = 0; k < 3; ++k) obs_out[k] = o[k];
   } else {
     float s[4] = {st[0], st[1], st[2], st[3]};
-    const bool term = cartpole_step(s, action);
+    const bool term = cartpole_step(s, (int)action);
     const float steps = st[4] + 1.f;
     d = term || steps >= (float)episode_limit;
     r = 1.0f;
@@ -108,9 +181,9 @@ __device__ inline void env_step_state(float* __restrict__ st, float* __restrict_
 // the same on the state arrays in memory (the stand-alone env_step_kernel's body)
 template <int ENV>
 __device__ inline void env_step_one(float* __restrict__ env_state, float* __restrict__ ep_stats, int n, int D,
-                                    uint64_t seed, int episode_limit, uint64_t tg, int action,
+                                    uint64_t seed, int episode_limit, uint64_t tg, float action,
                                     float* __restrict__ obs_out, float& r, bool& d) {
-  constexpr int W = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : CARTPOLE_STATE_W;
+  constexpr int W = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : ENV == ORL_ENV_PENDULUM ? PENDULUM_STATE_W : CARTPOLE_STATE_W;
   env_step_state<ENV>(env_state + (size_t)n * W, ep_stats != nullptr ? ep_stats + (size_t)n * 4 : nullptr, n, D, seed,
                       episode_limit, tg, action, obs_out, r, d);
 }

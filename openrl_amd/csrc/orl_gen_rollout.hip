@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64 * WAVES) void gen_rollout_kernel(MlpArgs A, ActA
         S.actions[((size_t)t * N + n) * a_w + k] = al[k];
         S.logp[((size_t)t * N + n) * a_w + k] = al[a_w + k];
       }
-      const int action = ENV == ORL_ENV_SYNTH ? 0 : (int)al[0];
+      const float action = ENV == ORL_ENV_SYNTH ? 0.f : al[0];
       float r;
       bool d;
       const size_t s1 = (size_t)(t + 1) * N + n;

@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256, 1) void rnn_rollout_single_policy_kernel(RnnRo
       bool d;
       float* orow = slab + j * DP;  // the next observation lands in the slab (next step's fc1) and in slot t + 1
       env_step_one<ENV>(A.env_state, A.ep_stats, env, D, A.env_seed, A.world_length, A.env_step0 + (uint64_t)t,
-                        ENV == ORL_ENV_SYNTH ? 0 : (int)act_o[0], orow, r, d);
+                        ENV == ORL_ENV_SYNTH ? 0.f : act_o[0], orow, r, d);
       const size_t s1 = (size_t)(t + 1) * N + row;
       for (int k = 0; k < D; ++k) b.policy_obs[s1 * D + k] = orow[k];
       b.rewards[(size_t)t * N + row] = r;

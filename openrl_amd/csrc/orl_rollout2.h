@@ -1,5 +1,5 @@
-// orl_rollout2.h - round 6: the fused rollout of the single-agent device envs (synthetic fixed-step env, CartPole-v1) as ONE
-// dependent chain per 16-env tile with everything else taken off it (included by orl_act.hip, inside namespace orl).
+// orl_rollout2.h - round 6: the fused rollout of the single-agent device envs (synthetic fixed-step env, CartPole-v1, tic-tac-toe
+// vs the random opponent, Pendulum-v1) as ONE dependent chain per 16-env tile with everything else taken off it (included by orl_act.hip, inside namespace orl).
 //
 // What the round-5 kernel (rollout_kernel, still built: tic-tac-toe runs on it, args.opp_reserved = 1 selects it for A/B) did
 // per step: policy AND critic tower in lock step on the same four SIMDs (an fp32 MFMA occupies the SIMD's VALU datapath, so the
@@ -26,7 +26,9 @@
 //     tile.  Values are not needed to act;
 //   * waves 5-7 ("services") run AHEAD of or BEHIND the chain through small LDS rings: wave 5 draws the sampling noise two steps
 //     ahead, wave 6 the action-independent half of the env step (synthetic: reward + next observation; CartPole: cos / sin of
-//     the pole angle and the reset state of the next episode - cartpole_pre / cartpole_reset), wave 7 writes the step's rows of
+//     the pole angle and the reset state of the next episode - cartpole_pre / cartpole_reset; Pendulum: the gravity term, the
+//     action-independent cost and the next episode's reset state with its observation - pendulum_pre / pendulum_reset), wave 7
+//     writes the step's rows of
 //     the rollout buffer (coalesced: the 16 rows of a field are contiguous) from an LDS staging ring.  Waves 4 and 8 exit: they
 //     would share wave 0's SIMD;
 //   * all hand-overs are single-writer LDS words (monotonic step counters) polled by their readers - LDS operations of a CU
@@ -56,7 +58,7 @@ __host__ __device__ inline Ro2Lds ro2_lds(int policy_total, int critic_total, in
   int o = policy_total;
   L.critic = o; o += critic_total;
   L.obs = o; o += RO2_ORING * TILE_B * DP;
-  L.word = o; o += RO2_ORING * TILE_B * 3;  // tic-tac-toe: [slot]{board word, opponent moves, episode}[row]
+  L.word = o; o += RO2_ORING * TILE_B * 3;  // tic-tac-toe: [slot]{board word, opponent moves, episode}[row]; Pendulum: [slot]{th, thdot}[row]
   L.xg = o; o += 2 * TILE_B * GS;
   L.part = o; o += 2 * 4 * (TILE_B * 16 + 4 * TILE_B * 2);  // [slot][wave]{16 x 16 logits | [q][row] 2 stats}; narrow heads use the head of it
   L.z2 = o; o += 2 * TILE_B * GS;
@@ -183,6 +185,16 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
   int* s_word = (int*)(smem + L.word);               // [slot][16]
   int* s_meta = s_word + RO2_ORING * TILE_B;        // [slot][2][16]: opponent moves this game, episode
   auto ttt_operand_bits = [&](int w) -> int { return (w >> ((q & 1) * 9 + (q >> 1))) & (q < 2 ? 0x155 : 0x55); };
+  // Pendulum-v1 (ORL_ENV_PENDULUM): the observation (cos th, sin th, thdot) does not give th back bit for bit, so every
+  // observation slot carries the state {th, thdot} it was made from (the word ring: [slot][2][16] floats) - wave 6 computes the
+  // action-independent half of the step from it while the policy works
+  constexpr bool IS_PEND = ENV == ORL_ENV_PENDULUM;
+  float* s_pst = smem + L.word;
+  if (IS_PEND && threadIdx.x < TILE_B) {
+    const int nn = n0 + threadIdx.x;
+    s_pst[threadIdx.x] = nn < N ? A.r.env_state[(size_t)nn * PENDULUM_STATE_W + 0] : 0.f;
+    s_pst[TILE_B + threadIdx.x] = nn < N ? A.r.env_state[(size_t)nn * PENDULUM_STATE_W + 1] : 0.f;
+  }
   if (IS_TTT && threadIdx.x < TILE_B) {
     const int jj = threadIdx.x, nn = n0 + jj;
     int ta = 0, to = 0, mv = 0, epi = 0;
@@ -273,7 +285,7 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
       smem[L.gtab + 32 + l] = ls + 0.91893853320467274178f;
     }
     // env state of the tile's rows (every lane of a row keeps a copy; lanes q == 0 write)
-    constexpr int SW = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : IS_TTT ? 0 : CARTPOLE_STATE_W;  // (tic-tac-toe: bitboards below)
+    constexpr int SW = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : IS_TTT ? 0 : IS_PEND ? PENDULUM_STATE_W : CARTPOLE_STATE_W;  // (tic-tac-toe: bitboards below)
     float est[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float ep_ret = 0.f, ep_len = 0.f, fin_ret = 0.f, fin_cnt = 0.f;
     if (gw == 0 && ok) {
@@ -439,7 +451,7 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
         if constexpr (HMM && HEAD == ORL_HEAD_GAUSSIAN) nz4 = ro2_ld4f(noise + 4 * q);
         else nz4 = ro2_ld4f(noise);
         envr0 = ro2_ld4f(er);
-        if (ENV == ORL_ENV_CARTPOLE) envr1 = ro2_ld4f(er + 4);
+        if (ENV == ORL_ENV_CARTPOLE || IS_PEND) envr1 = ro2_ld4f(er + 4);
         // slot (t + 1) & 7 of the observation ring held observation t - 7: the critic wave of step t - 7 has read it when its
         // flag says so; the staging / env rings (4 deep) are free once the store wave has finished step t - 4
         const int need_c = t - 6;
@@ -591,6 +603,29 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
           s_word[sl * TILE_B + j] = ok ? (tA | (tO << 9) | (1 << 18)) : 0;
           s_meta[sl * 2 * TILE_B + j] = tmoves; s_meta[sl * 2 * TILE_B + TILE_B + j] = tep;
         }
+      } else if constexpr (IS_PEND) {
+        // the torque clip, the action's cost, two FMAs, the speed clip, the wrap and sincos of the new angle; the auto-reset state
+        // and its observation came from wave 6 (env record: {grav, cost0, reset th, reset thdot | reset cos, reset sin})
+        PendulumPre pp;
+        pp.grav = envr0[0]; pp.cost0 = envr0[1];
+        float s[2] = {est[0], est[1]}, o[3];
+        rew = pendulum_post(pp, s, act0, o);
+        const float steps = est[2] + 1.f;
+        done = steps >= (float)A.r.episode_limit;  // never terminates: truncation only
+        est[2] = done ? 0.f : steps;
+        est[3] += done ? 1.f : 0.f;
+        est[0] = done ? envr0[2] : s[0];
+        est[1] = done ? envr0[3] : s[1];
+        o[0] = done ? envr1[0] : o[0];
+        o[1] = done ? envr1[1] : o[1];
+        o[2] = est[1];
+        const int sl = (t + 1) & (RO2_ORING - 1);
+        float* nxt = s_obs + sl * TILE_B * DP;
+        if (q == 0) {
+          *(f32x4*)(nxt + j * DP) = ok ? f32x4{o[0], o[1], o[2], 0.f} : f32x4{0.f, 0.f, 0.f, 0.f};
+          s_pst[sl * 2 * TILE_B + j] = est[0];
+          s_pst[sl * 2 * TILE_B + TILE_B + j] = est[1];
+        }
       } else {
         CartPolePre cp;
         cp.costh = envr0[0]; cp.sinth = envr0[1]; cp.t1 = envr0[2]; cp.den = envr0[3];
@@ -656,7 +691,9 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
     }
   } else if (wave == 6) {
     // ================================================================ the action-independent half of env.step =====
-    float ep = (ENV == ORL_ENV_CARTPOLE && ok) ? A.r.env_state[(size_t)n * CARTPOLE_STATE_W + 5] : 0.f;
+    float ep = (ENV == ORL_ENV_CARTPOLE && ok) ? A.r.env_state[(size_t)n * CARTPOLE_STATE_W + 5]
+               : (IS_PEND && ok)                 ? A.r.env_state[(size_t)n * PENDULUM_STATE_W + 3]
+                                                 : 0.f;
     for (int t = 0; t < T; ++t) {
       float* er = smem + L.env + ((t & 3) * TILE_B + j) * RO2_ENVW;
       const uint64_t tg = tg0 + (uint64_t)t;
@@ -685,6 +722,19 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
         const int* mt = s_meta + (t & (RO2_ORING - 1)) * 2 * TILE_B;
         const int mv = mt[j], epi = mt[TILE_B + j];
         if (q < 3) er[q] = u2f(ttt_draw(A.r.env_seed, (uint32_t)n, q, (uint32_t)(epi + (q != 0 ? 1 : 0)), (uint32_t)mv));
+      } else if constexpr (IS_PEND) {
+        // pendulum_pre of state t (published with observation t) and the next episode's reset state + observation
+        ro2_wait(ctr + RC_OBS, t + 1, err);
+        if (t >= 1) ep += smem[L.stage + (((t - 1) & 3) * TILE_B + j) * RO2_STG + 33];  // done of step t - 1 (staged before obs t)
+        const float* ps = s_pst + (t & (RO2_ORING - 1)) * 2 * TILE_B;
+        const PendulumPre pp = pendulum_pre(ps[j], ps[TILE_B + j]);
+        float rs[2], ro[3];
+        pendulum_reset(A.r.env_seed, (uint32_t)n, (uint32_t)(ep + 1.f), rs);
+        pendulum_obs(rs, ro);
+        if (q == 0) {
+          *(f32x4*)er = f32x4{pp.grav, pp.cost0, rs[0], rs[1]};
+          *(f32x4*)(er + 4) = f32x4{ro[0], ro[1], 0.f, 0.f};
+        }
       } else {
         ro2_wait(ctr + RC_OBS, t + 1, err);
         if (t >= 1) ep += smem[L.stage + (((t - 1) & 3) * TILE_B + j) * RO2_STG + 33];  // done of step t - 1 (staged before obs t)

@@ -8,12 +8,19 @@ batch_rewards(buffer), statistics(buffer), close()``.
 
 State lives in HBM; ``step`` launches ``orl_env_step``; the fused driver never calls ``step`` at all -
 it hands ``device_handle()`` to ``orl_rollout_fused`` which advances the same state in-kernel.
-Two kinds are built:
+Three kinds are built:
 
 * ``synthetic``: the fixed-step benchmark env - obs ~ N(0,1) keyed (seed, env, t), reward U(0,1),
   episodes of exactly ``episode_limit`` steps with per-env phase (env*7) mod limit, no bad transitions;
 * ``cartpole``: CartPole-v1 dynamics (gymnasium classic_control, euler integrator, fp32), 500-step limit,
-  auto-reset, ``done = terminated or truncated`` (RemoveTruncated, envs/wrappers/extra_wrappers.py:122-134).
+  auto-reset, ``done = terminated or truncated`` (RemoveTruncated, envs/wrappers/extra_wrappers.py:122-134);
+* ``pendulum``: Pendulum-v1 dynamics (gymnasium classic_control/pendulum.py, fp32), observation
+  ``(cos th, sin th, thdot)`` in ``Box([-1, -1, -8], [1, 1, 8])``, action ``Box(-2, 2, (1,))`` (clipped in the env,
+  stored unclipped like the reference), reward ``-(angle_normalize(th)^2 + 0.1 thdot^2 + 0.001 u^2)``, never terminates,
+  truncated at 200 steps with the same ``done`` / auto-reset semantics.  Reset states ``th ~ U(-pi, pi)``,
+  ``thdot ~ U(-1, 1)`` come from the engine's own Philox stream keyed ``(seed, env, episode)``, as CartPole's do.
+  One deviation from gymnasium's float64: ``th`` is wrapped back to ``[-pi, pi)`` after every step (csrc/orl_env.h) -
+  the same in real arithmetic, and it keeps the fp32 angle increment and ``sinf`` / ``cosf`` accurate.
 
 Env ``i`` is seeded ``seed + i*10086`` in the reference (sync_venv.py:136-137); here the counter-based
 generator is keyed by ``(seed, i)`` which gives every lane its own stream the same way.
@@ -34,12 +41,16 @@ class DeviceVecEnv:
     def __init__(self, kind: str, env_num: int, obs_dim: int, action_space, env_name: str, episode_limit: int,
                  device="cuda:0", seed: int = 0):
         self.kind = kind
-        self.env_kind = {"synthetic": ops.ENV_SYNTH, "cartpole": ops.ENV_CARTPOLE}[kind]
+        self.env_kind = {"synthetic": ops.ENV_SYNTH, "cartpole": ops.ENV_CARTPOLE, "pendulum": ops.ENV_PENDULUM}[kind]
         self.device = nat.require_gpu(device)
         self._n = int(env_num)
         self._obs_dim = int(obs_dim)
         self._action_space = action_space
-        self._observation_space = spaces.Box(-np.inf, np.inf, (obs_dim,), np.float32)
+        if kind == "pendulum":
+            self._observation_space = spaces.Box(np.array([-1.0, -1.0, -8.0], np.float32),
+                                                 np.array([1.0, 1.0, 8.0], np.float32), (obs_dim,), np.float32)
+        else:
+            self._observation_space = spaces.Box(-np.inf, np.inf, (obs_dim,), np.float32)
         self._env_name = env_name
         self.episode_limit = int(episode_limit)
         self.seed = int(seed)
