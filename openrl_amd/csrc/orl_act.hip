@@ -880,7 +880,7 @@ __global__ __launch_bounds__(512) void rollout_kernel(RolloutArgs A) {
 
 // V(obs) for a large batch of stored observations (all T+1 slots of a rollout in one launch): persistent workgroups
 // of 8 waves, the critic tower staged once per workgroup, one 16-row tile per wave and trip, the next tile's
-// observation fragments prefetched into registers.  Per-row arithmetic = act_step_kernel's critic wave (trunk_fwd_T).
+// observation fragments (its first 64 columns) prefetched into registers.  Per-row arithmetic = act_step_kernel's critic wave (trunk_fwd_T).
 __global__ __launch_bounds__(512) void critic_values_kernel(orl_net_desc cnet, const float* __restrict__ ctheta,
                                                             const float* __restrict__ obs, long long rows,
                                                             float* __restrict__ values, float* __restrict__ tail_out,
@@ -912,7 +912,13 @@ __global__ __launch_bounds__(512) void critic_values_kernel(orl_net_desc cnet, c
 #pragma unroll
     for (int s = 0; s < 16; ++s) xc[s] = xr[s];
     fetch(tile + stride);
+    const long long row = tile * TILE_B + j;
+    const bool row_ok = row < rows;
     auto xb = [&](int s) -> float {
+      if (s >= 16) {  // observations wider than 64 columns: k-steps past the prefetched 16 read global memory
+        const int k = 4 * s + q;
+        return (row_ok && k < D) ? obs[row * D + k] : 0.f;
+      }
       float v = xc[0];
 #pragma unroll
       for (int t = 1; t < 16; ++t) v = (s == t) ? xc[t] : v;
@@ -922,8 +928,7 @@ __global__ __launch_bounds__(512) void critic_values_kernel(orl_net_desc cnet, c
     trunk_fwd_T(smem, tw, xb, j, q, n2);
     float v[1];
     head_T<1>(smem + tw.W3, smem + tw.b3, 1, n2, q, v);
-    const long long row = tile * TILE_B + j;
-    if (row < rows && q == 0) {
+    if (row_ok && q == 0) {
       values[row] = v[0];
       if (tail_out != nullptr && row >= tail_row0) tail_out[row - tail_row0] = v[0];
     }
@@ -1382,13 +1387,14 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
                                                ORL_TOWER_F16 != 0).total,
                                       TowerLds(cnet->obs_dim, 1, false, false, false, true).total, twp.DP).total *
                       sizeof(float);
-  // (the widest towers - observations of ~60 columns with 16 outputs - do not fit the chain kernel's rings beside both tower
-  // images: they keep the round-5 kernel)
+  // The chain kernel takes observations of at most 64 columns (DP <= 64): its critic waves hold one row's observation in 16
+  // registers of 4 columns each.  Wider observations (and towers whose rings do not fit beside both images, from obs 65
+  // with more than 2 outputs) keep the round-5 kernel, whose fc1 loops over every k-step.
   // (Pendulum's towers - obs 3, one output - are far below the LDS limit: the fallback below never has to take it)
   if (pend && lds2 > 160 * 1024)
     return fail(ORL_E_INVALID, "orl_rollout_fused: Pendulum's chain kernel needs %zu B of LDS (> 160 KiB)", lds2);
   if ((args->env_kind == ORL_ENV_SYNTH || args->env_kind == ORL_ENV_CARTPOLE || args->env_kind == ORL_ENV_TTT || pend) &&
-      args->opp_reserved != 1 && lds2 <= 160 * 1024) {
+      args->opp_reserved != 1 && twp.DP <= 64 && lds2 <= 160 * 1024) {
 #define ORL_RO2_LAUNCH3(NO, HD, EV, KS)                                                                               \
   do {                                                                                                               \
     if (lds2 > 48 * 1024)                                                                                            \

@@ -30,13 +30,20 @@ from .ppo_module import FusedAdam, PPOModule, ValueNorm
 GAINS = ["tanh", "relu", "leaky_relu", "selu"]  # calculate_gain names per activation_id (mlp.py:15-17)
 
 
-def needs_generic(cfg, act_space, share_model: bool) -> bool:
-    """Does this configuration fall outside the fused default-tower kernels?"""
+# widest observation the default towers' update kernels take (check_net of orl_ppo.hip and orl_rnn.hip)
+DEFAULT_TOWER_MAX_OBS = 64
+
+
+def needs_generic(cfg, act_space, share_model: bool, obs_dims=()) -> bool:
+    """Does this configuration fall outside the fused default-tower kernels?  ``obs_dims``: the towers' observation
+    widths; one wider than ``DEFAULT_TOWER_MAX_OBS`` goes to the general towers (feed-forward and recurrent alike)."""
     kind = spaces.kind(act_space)
     stacked = bool(cfg.use_recurrent_policy or cfg.use_naive_recurrent_policy) and (
         cfg.recurrent_N != 1 or getattr(cfg, "rnn_type", "gru") != "gru")  # GRU stacks and LSTMs: the general towers
+    wide = any(int(d) > DEFAULT_TOWER_MAX_OBS for d in obs_dims)
     return bool(share_model or cfg.use_share_model or cfg.layer_N != 1 or cfg.hidden_size != 64
-                or cfg.activation_id != 1 or cfg.use_feature_normalization or kind in ("MultiDiscrete", "Tuple") or stacked)
+                or cfg.activation_id != 1 or cfg.use_feature_normalization or kind in ("MultiDiscrete", "Tuple") or stacked
+                or wide)
 
 
 def _act_head(act_space):

@@ -276,11 +276,14 @@ class PPOModule:
     def __new__(cls, cfg, policy_input_space=None, critic_input_space=None, act_space=None, share_model: bool = False,
                 *args, **kwargs):
         # Configurations outside the fused default tower (hidden_size / layer_N / activation / feature norm / shared
-        # model / MultiDiscrete) are served by GenericPPOModule behind the same constructor.
+        # model / MultiDiscrete / observations wider than 64 columns) are served by GenericPPOModule behind the same
+        # constructor.
         if cls is PPOModule and act_space is not None:
             from .generic_net import GenericPPOModule, needs_generic
 
-            if needs_generic(cfg, act_space, share_model):  # recurrent or not: GenNet carries the GRU too
+            dims = [spaces.obs_dim(sel(sp)) for sel, sp in ((spaces.policy_obs_space, policy_input_space),
+                                                            (spaces.critic_obs_space, critic_input_space)) if sp is not None]
+            if needs_generic(cfg, act_space, share_model, dims):  # recurrent or not: GenNet carries the GRU too
                 return object.__new__(GenericPPOModule)
         return object.__new__(cls)
 

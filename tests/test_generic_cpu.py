@@ -50,6 +50,20 @@ def test_dispatch_rule_and_state_dict_keys():
     assert not gn.needs_generic(base, spaces.Box(-1, 1, (3,)), False)
     assert gn.needs_generic(base, spaces.MultiDiscrete([3, 2]), False)
     assert gn.needs_generic(base, spaces.Discrete(2), True)
+    # observations wider than the default towers' update kernels take (64 columns), in either tower
+    assert not gn.needs_generic(base, spaces.Discrete(2), False, [64, 64])
+    assert gn.needs_generic(base, spaces.Discrete(2), False, [65, 65])
+    assert gn.needs_generic(base, spaces.Box(-1, 1, (3,)), False, [4, 100])
+    rec = default_cfg(["--use_recurrent_policy", "true"])
+    assert not gn.needs_generic(rec, spaces.Discrete(2), False, [64, 64])
+    assert gn.needs_generic(rec, spaces.Discrete(2), False, [100, 100])
+    from openrl_amd.modules.ppo_module import PPOModule
+
+    wide, narrow = spaces.Box(-1, 1, (100,)), spaces.Box(-1, 1, (64,))
+    assert PPOModule.__new__(PPOModule, base, wide, wide, spaces.Discrete(3)).__class__ is gn.GenericPPOModule
+    assert PPOModule.__new__(PPOModule, base, narrow, narrow, spaces.Discrete(3)).__class__ is PPOModule
+    both = spaces.Dict({"policy": narrow, "critic": wide})
+    assert PPOModule.__new__(PPOModule, base, both, both, spaces.Discrete(3)).__class__ is gn.GenericPPOModule
     for argv in (["--hidden_size", "128"], ["--layer_N", "2"], ["--activation_id", "0"],
                  ["--use_feature_normalization", "true"], ["--use_share_model", "true"]):
         assert gn.needs_generic(default_cfg(argv), spaces.Discrete(2), False), argv

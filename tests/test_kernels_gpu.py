@@ -124,16 +124,19 @@ def test_grouped_act_step_equals_one_launch_per_policy(ops):
     assert len(torch.unique(a1)) > 3
 
 
-@pytest.mark.parametrize("D,B", [(4, 1000), (18, 4099), (54, 33)])
+@pytest.mark.parametrize("D,B", [(4, 1000), (18, 4099), (54, 33), (65, 37), (100, 1000), (256, 33)])
 def test_batched_critic_values_equal_the_act_step_critic(ops, D, B):
-    """orl_critic_values (the fused rollout's value pass over all T+1 slots) == orl_act_step's critic wave, bit for bit."""
+    """orl_critic_values (the fused rollout's value pass over all T+1 slots) == orl_act_step's critic wave, bit for bit -
+    also past 64 columns, where orl_critic_values' register prefetch ends and its k-steps read global memory."""
     rs = np.random.RandomState(D)
     cnet = ops.net_desc(D, 1, ops.HEAD_VALUE)
     n_par = D * 64 + 64 * 3 + 64 * 64 + 64 * 3 + 64 + 1
     theta = dev((0.2 * rs.randn(n_par)).astype(np.float32))
     obs = dev(rs.randn(B, D).astype(np.float32))
     want, got = torch.empty(B, 1, device=DEV), torch.full((B,), np.nan, device=DEV)
-    pnet = ops.net_desc(D, 2, ops.HEAD_CATEGORICAL)  # descriptor only: no policy parameters are passed
+    # descriptor only: no policy parameters are passed (its LDS image is still reserved: past 64 columns a 1-column one
+    # leaves room for the widest critic)
+    pnet = ops.net_desc(D if D <= 64 else 1, 2, ops.HEAD_CATEGORICAL)
     ops.act_step(pnet, None, cnet, theta, None, obs, None, B, True, 0, 0, 0, None, want, None, None)
     ops.critic_values(cnet, theta, obs, got)
     assert torch.equal(got, want.view(-1))

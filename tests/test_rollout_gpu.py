@@ -336,8 +336,9 @@ def test_cartpole_learns_like_the_reference_recipe(tmp_path):
 
 @pytest.mark.parametrize("obs_dim,act", [(64, ("discrete", 16)), (33, ("box", 16)), (1, ("discrete", 2))])
 def test_extreme_tower_shapes_train_end_to_end(obs_dim, act):
-    """The widest (obs 64, 16 outputs) and narrowest towers the kernels admit through make / PPONet / PPOAgent.train on
-    the synthetic env: fused rollout, GAE, update - finite parameters, permutation and buffers consistent."""
+    """The widest (obs 64, 16 outputs) and narrowest towers the default towers' update kernels admit through make / PPONet /
+    PPOAgent.train on the synthetic env: fused rollout, GAE, update - finite parameters, permutation and buffers
+    consistent.  (Wider observations train on the general towers: test_tower_envelope_gpu.py.)"""
     from openrl_amd import spaces
     from openrl_amd.envs.common import make
     from openrl_amd.modules.common import PPONet as Net
