@@ -422,6 +422,12 @@ int orl_minibatch_moments(const float* records, int rec_width, int ret_col, cons
 #define ORL_ENV_PENDULUM 5 /* Pendulum-v1 dynamics (gymnasium classic_control pendulum.py, fp32, th wrapped to [-pi, pi) every
                             * step): obs 3 (cos th, sin th, thdot), Box(-2, 2, (1,)) float actions, never terminates.  Fused
                             * rollout: the chain kernel only (Gaussian head, n_out 1, obs_dim 3; opp_reserved 1 is rejected) */
+#define ORL_ENV_ACROBOT 6  /* Acrobot-v1 dynamics (gymnasium classic_control acrobot.py, book dynamics, RK4, fp32): obs 6 (cos th1,
+                            * sin th1, cos th2, sin th2, dth1, dth2), Discrete(3) torques {-1, 0, +1}, reward -1 / 0 on the terminal
+                            * step.  Fused rollout: the chain kernel only (Discrete(3), obs_dim 6; opp_reserved 1 is rejected) */
+#define ORL_ENV_MOUNTAINCAR 7 /* MountainCar-v0 dynamics (gymnasium classic_control mountain_car.py, fp32): obs 2 (position,
+                               * velocity), Discrete(3), reward -1.  Fused rollout: the chain kernel only (Discrete(3), obs_dim 2;
+                               * opp_reserved 1 is rejected) */
 
 typedef struct orl_rollout_args {
   orl_buffer_ptrs buf;
@@ -439,7 +445,7 @@ typedef struct orl_rollout_args {
   const float* opp_thetas; /* parameters of policy g at opp_thetas + g*opp_theta_stride */
   int64_t opp_theta_stride;
   int32_t opp_group_rows;  /* envs [g*opp_group_rows, ...) play policy g; a multiple of 16 */
-  int32_t opp_reserved;    /* ORL_ENV_SYNTH / ORL_ENV_CARTPOLE / ORL_ENV_TTT / ORL_ENV_PENDULUM: 0 = the round-6 chain rollout (policy-only step chain, the
+  int32_t opp_reserved;    /* ORL_ENV_SYNTH / ORL_ENV_CARTPOLE / ORL_ENV_TTT / ORL_ENV_PENDULUM / ORL_ENV_ACROBOT / ORL_ENV_MOUNTAINCAR: 0 = the round-6 chain rollout (policy-only step chain, the
                             * critic on background waves of the same launch), 1 = the round-5 kernel (both towers in the
                             * step loop).  Ignored by the tic-tac-toe POOL envs (always the round-5 kernel). */
   uint64_t opp_seed;       /* Philox seed of the opponents' sampling; counter = (env, opp_rng_step0 + t) */

@@ -1,5 +1,5 @@
 // orl_env.h - the device-resident single-agent envs (synthetic fixed-step env of SURVEY.md section 8d, CartPole-v1,
-// Pendulum-v1) as per-env device functions, shared by the fused rollout kernels (orl_act.hip: default towers,
+// Pendulum-v1, Acrobot-v1, MountainCar-v0) as per-env device functions, shared by the fused rollout kernels (orl_act.hip: default towers,
 // orl_gen_fused.hip: general towers) and the stand-alone env kernels: one definition, so every route steps an env with the same arithmetic and the
 // same Philox streams.  Not part of the C ABI.
 #pragma once
@@ -126,6 +126,134 @@ __device__ inline void pendulum_obs(const float (&s)[2], float* __restrict__ obs
   obs[0] = cs; obs[1] = sn; obs[2] = s[1];
 }
 
+// --------------------------------------------------------------------------------------------------
+// Acrobot-v1 and MountainCar-v0 (gymnasium classic_control acrobot.py / mountain_car.py) in fp32, Discrete(3) actions.
+//
+// Written for reproducible arithmetic in translation units built with -ffast-math (orl_act.hip): the functions below turn
+// off reassociation and implicit contraction (ORL_CC_FP_EXACT - every fused multiply-add is an explicit fmaf), and the
+// trigonometry calls the device library's accurate sin / cos / sincos (__ocml_*_f32: what sinf / cosf / sincosf are
+// without -ffast-math; with it the header maps sinf / cosf to the __sinf / __cosf hardware approximations).  Divisions
+// are the translation unit's (-ffast-math: a correctly scaled reciprocal and a product, within 1 ulp of IEEE).  So an env
+// steps through the same operations, bit for bit, wherever it is inlined.
+//
+// Deviations from gymnasium, both for Acrobot:
+//   * fp32 instead of float64 (gymnasium's np.append promotes the state to float64);
+//   * cos(x - pi/2) is written as sin(x) (equal in real arithmetic), and the unit masses / lengths / inertias are folded
+//     into the constants of _dsdt (d1 = 3.5 + cos th2, d2 = 1.25 + 0.5 cos th2, d2^2 / d1 = d2 (d2 / d1)).
+// The wrap of th1 / th2 into [-pi, pi] is gymnasium's while loop, bounded at 16 turns each way: the states reachable in a
+// step (|th| <= pi + dt |dth| with the bounded speeds and RK4's intermediate ones) never need more than a few.
+// Reset states come from the engine's own Philox stream keyed (seed, env, episode), as CartPole's do.
+// --------------------------------------------------------------------------------------------------
+constexpr int ACROBOT_STATE_W = 6;      // {th1, th2, dth1, dth2, steps_in_episode, episodes}
+constexpr int MOUNTAINCAR_STATE_W = 4;  // {position, velocity, steps_in_episode, episodes}
+// at the start of every function body below: no reassociation, no contraction but the explicit fmaf
+#define ORL_CC_FP_EXACT _Pragma("clang fp reassociate(off) contract(off)")
+constexpr float ACRO_PI = 3.14159265358979323846f, ACRO_2PI = 6.28318530718f;
+constexpr float ACRO_MAX_VEL_1 = 4.0f * 3.14159265358979323846f, ACRO_MAX_VEL_2 = 9.0f * 3.14159265358979323846f;
+__device__ inline float cc_sin(float x) { return __ocml_sin_f32(x); }
+__device__ inline float cc_cos(float x) { return __ocml_cos_f32(x); }
+__device__ inline void cc_sincos(float x, float& s, float& c) {
+  float ct;
+  s = __ocml_sincos_f32(x, (__attribute__((opencl_private)) float*)&ct);
+  c = ct;
+}
+__device__ inline void acrobot_reset(uint64_t seed, uint32_t env, uint32_t episode, float (&s)[4]) {
+  ORL_CC_FP_EXACT
+  const u4 r = philox4x32_10(seed, env, 0xAC40B000u, episode, 0u);
+  s[0] = fmaf(u01(r.x), 0.2f, -0.1f);
+  s[1] = fmaf(u01(r.y), 0.2f, -0.1f);
+  s[2] = fmaf(u01(r.z), 0.2f, -0.1f);
+  s[3] = fmaf(u01(r.w), 0.2f, -0.1f);
+}
+// _dsdt (book dynamics) of state s under torque a: returns (dth1, dth2, ddth1, ddth2)
+__device__ inline void acrobot_dsdt(const float (&s)[4], float a, float (&ds)[4]) {
+  ORL_CC_FP_EXACT
+  float s2, c2;
+  cc_sincos(s[1], s2, c2);
+  const float s1 = cc_sin(s[0]);
+  const float s12 = cc_sin(s[0] + s[1]);
+  const float d1 = 3.5f + c2;
+  const float d2 = fmaf(0.5f, c2, 1.25f);
+  const float phi2 = 4.9f * s12;
+  const float w = fmaf(s[3], s[3], (2.0f * s[3]) * s[2]);  // dth2^2 + 2 dth2 dth1
+  const float phi1 = fmaf(-0.5f * s2, w, fmaf(14.7f, s1, phi2));
+  const float r = d2 / d1;
+  const float num = fmaf(-0.5f * s2, s[2] * s[2], fmaf(r, phi1, a)) - phi2;
+  const float dd2 = num / fmaf(-d2, r, 1.25f);
+  const float dd1 = -fmaf(d2, dd2, phi1) / d1;
+  ds[0] = s[2]; ds[1] = s[3]; ds[2] = dd1; ds[3] = dd2;
+}
+__device__ inline float acrobot_wrap(float x) {
+  ORL_CC_FP_EXACT
+#pragma unroll 1
+  for (int i = 0; i < 16 && x > ACRO_PI; ++i) x = x - ACRO_2PI;
+#pragma unroll 1
+  for (int i = 0; i < 16 && x < -ACRO_PI; ++i) x = x + ACRO_2PI;
+  return x;
+}
+// One step of state s (in / out) under action a in {0, 1, 2} (torque a - 1): rk4 over [0, dt], the wrap, the speed bounds;
+// writes the observation (cos th1, sin th1, cos th2, sin th2, dth1, dth2) and returns whether the new state is terminal.
+__device__ inline bool acrobot_step(float (&s)[4], int a, float (&obs)[6]) {
+  ORL_CC_FP_EXACT
+  const float torque = (float)(a - 1), dt = 0.2f, dt2 = 0.1f, dt6 = 0.2f / 6.0f;
+  float k1[4], k2[4], k3[4], k4[4], y[4];
+  acrobot_dsdt(s, torque, k1);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = fmaf(dt2, k1[i], s[i]);
+  acrobot_dsdt(y, torque, k2);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = fmaf(dt2, k2[i], s[i]);
+  acrobot_dsdt(y, torque, k3);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = fmaf(dt, k3[i], s[i]);
+  acrobot_dsdt(y, torque, k4);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = fmaf(dt6, fmaf(2.0f, k3[i], fmaf(2.0f, k2[i], k1[i])) + k4[i], s[i]);
+  s[0] = acrobot_wrap(y[0]);
+  s[1] = acrobot_wrap(y[1]);
+  s[2] = fminf(fmaxf(y[2], -ACRO_MAX_VEL_1), ACRO_MAX_VEL_1);
+  s[3] = fminf(fmaxf(y[3], -ACRO_MAX_VEL_2), ACRO_MAX_VEL_2);
+  float sn1, cs1, sn2, cs2;
+  cc_sincos(s[0], sn1, cs1);
+  cc_sincos(s[1], sn2, cs2);
+  obs[0] = cs1; obs[1] = sn1; obs[2] = cs2; obs[3] = sn2; obs[4] = s[2]; obs[5] = s[3];
+  return -cs1 - cc_cos(s[1] + s[0]) > 1.0f;
+}
+__device__ inline void acrobot_obs(const float (&s)[4], float (&obs)[6]) {
+  float sn1, cs1, sn2, cs2;
+  cc_sincos(s[0], sn1, cs1);
+  cc_sincos(s[1], sn2, cs2);
+  obs[0] = cs1; obs[1] = sn1; obs[2] = cs2; obs[3] = sn2; obs[4] = s[2]; obs[5] = s[3];
+}
+
+// MountainCar-v0: position p ~ U(-0.6, -0.4), velocity 0 at reset.  The step in two halves, as CartPole's: the gravity
+// term cos(3 p) (-0.0025) does not depend on the action (mountaincar_pre), the rest does (mountaincar_post).
+__device__ inline void mountaincar_reset(uint64_t seed, uint32_t env, uint32_t episode, float (&s)[2]) {
+  ORL_CC_FP_EXACT
+  const u4 r = philox4x32_10(seed, env, 0x3C4A0000u, episode, 0u);
+  s[0] = fmaf(u01(r.x), 0.2f, -0.6f);
+  s[1] = 0.0f;
+}
+__device__ inline float mountaincar_pre(float p) {
+  ORL_CC_FP_EXACT
+  return cc_cos(3.0f * p) * -0.0025f; }
+// s = {p, v} in / out; returns whether the new state is terminal (the reward is -1 on every step)
+__device__ inline bool mountaincar_post(float (&s)[2], float pre, int a) {
+  ORL_CC_FP_EXACT
+  float v = s[1] + fmaf((float)(a - 1), 0.001f, pre);
+  v = fminf(fmaxf(v, -0.07f), 0.07f);
+  float p = s[0] + v;
+  p = fminf(fmaxf(p, -1.2f), 0.6f);
+  if (p == -1.2f && v < 0.0f) v = 0.0f;
+  s[0] = p; s[1] = v;
+  return p >= 0.5f && v >= 0.0f;
+}
+// actions of the Discrete(3) envs as a class index: the float action is truncated and clamped into {0, 1, 2}
+__device__ inline int discrete3_action(float action) {
+  const int a = (int)action;
+  return a < 0 ? 0 : (a > 2 ? 2 : a);
+}
+
 // One env.step of env `n` at global time `tg` on the env's state row `st` / episode statistics `e` (register or memory
 // copies): writes the next observation to obs_out[0..D), returns the reward and whether the episode ended.  The one
 // definition of the envs' arithmetic: every route steps through it.
@@ -159,6 +287,33 @@ __device__ inline void env_step_state(float* __restrict__ st, float* __restrict_
     }
     st[0] = s[0]; st[1] = s[1];
     for (int k = 0; k < 3; ++k) obs_out[k] = o[k];
+  } else if (ENV == ORL_ENV_ACROBOT) {
+    float s[4] = {st[0], st[1], st[2], st[3]}, o[6];
+    const bool term = acrobot_step(s, discrete3_action(action), o);
+    const float steps = st[4] + 1.f;
+    d = term || steps >= (float)episode_limit;
+    r = term ? 0.f : -1.f;
+    st[4] = d ? 0.f : steps;
+    if (d) {
+      st[5] += 1.f;
+      acrobot_reset(seed, (uint32_t)n, (uint32_t)st[5], s);  // auto-reset: the first observation of the next episode
+      acrobot_obs(s, o);
+    }
+    for (int k = 0; k < 4; ++k) st[k] = s[k];
+    for (int k = 0; k < 6; ++k) obs_out[k] = o[k];
+  } else if (ENV == ORL_ENV_MOUNTAINCAR) {
+    float s[2] = {st[0], st[1]};
+    const bool term = mountaincar_post(s, mountaincar_pre(s[0]), discrete3_action(action));
+    const float steps = st[2] + 1.f;
+    d = term || steps >= (float)episode_limit;
+    r = -1.f;
+    st[2] = d ? 0.f : steps;
+    if (d) {
+      st[3] += 1.f;
+      mountaincar_reset(seed, (uint32_t)n, (uint32_t)st[3], s);
+    }
+    st[0] = s[0]; st[1] = s[1];
+    obs_out[0] = s[0]; obs_out[1] = s[1];
   } else {
     float s[4] = {st[0], st[1], st[2], st[3]};
     const bool term = cartpole_step(s, (int)action);
@@ -183,7 +338,11 @@ template <int ENV>
 __device__ inline void env_step_one(float* __restrict__ env_state, float* __restrict__ ep_stats, int n, int D,
                                     uint64_t seed, int episode_limit, uint64_t tg, float action,
                                     float* __restrict__ obs_out, float& r, bool& d) {
-  constexpr int W = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : ENV == ORL_ENV_PENDULUM ? PENDULUM_STATE_W : CARTPOLE_STATE_W;
+  constexpr int W = ENV == ORL_ENV_SYNTH         ? SYNTH_STATE_W
+                    : ENV == ORL_ENV_PENDULUM    ? PENDULUM_STATE_W
+                    : ENV == ORL_ENV_ACROBOT     ? ACROBOT_STATE_W
+                    : ENV == ORL_ENV_MOUNTAINCAR ? MOUNTAINCAR_STATE_W
+                                                 : CARTPOLE_STATE_W;
   env_step_state<ENV>(env_state + (size_t)n * W, ep_stats != nullptr ? ep_stats + (size_t)n * 4 : nullptr, n, D, seed,
                       episode_limit, tg, action, obs_out, r, d);
 }

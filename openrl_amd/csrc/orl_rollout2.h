@@ -1,5 +1,5 @@
 // orl_rollout2.h - round 6: the fused rollout of the single-agent device envs (synthetic fixed-step env, CartPole-v1, tic-tac-toe
-// vs the random opponent, Pendulum-v1) as ONE dependent chain per 16-env tile with everything else taken off it (included by orl_act.hip, inside namespace orl).
+// vs the random opponent, Pendulum-v1, Acrobot-v1, MountainCar-v0) as ONE dependent chain per 16-env tile with everything else taken off it (included by orl_act.hip, inside namespace orl).
 //
 // What the round-5 kernel (rollout_kernel, still built: tic-tac-toe runs on it, args.opp_reserved = 1 selects it for A/B) did
 // per step: policy AND critic tower in lock step on the same four SIMDs (an fp32 MFMA occupies the SIMD's VALU datapath, so the
@@ -27,7 +27,9 @@
 //   * waves 5-7 ("services") run AHEAD of or BEHIND the chain through small LDS rings: wave 5 draws the sampling noise two steps
 //     ahead, wave 6 the action-independent half of the env step (synthetic: reward + next observation; CartPole: cos / sin of
 //     the pole angle and the reset state of the next episode - cartpole_pre / cartpole_reset; Pendulum: the gravity term, the
-//     action-independent cost and the next episode's reset state with its observation - pendulum_pre / pendulum_reset), wave 7
+//     action-independent cost and the next episode's reset state with its observation - pendulum_pre / pendulum_reset;
+//     MountainCar: the gravity term cos(3 p) and the reset state; Acrobot: the WHOLE step under each of the three torques and,
+//     after a done, the reset record - wave 0 selects the sampled one), wave 7
 //     writes the step's rows of
 //     the rollout buffer (coalesced: the 16 rows of a field are contiguous) from an LDS staging ring.  Waves 4 and 8 exit: they
 //     would share wave 0's SIMD;
@@ -51,9 +53,16 @@ enum { RC_OBS = 0, RC_STAGE = 1, RC_NOISE = 4, RC_ENV = 5, RC_STORED = 6, RC_ERR
        RC_WORDS = 20 };
 
 struct Ro2Lds {
-  int critic, obs, word, xg, part, z2, noise, env, stage, gtab, ctr, total;  // float offsets
+  int critic, obs, word, xg, part, z2, noise, env, stage, gtab, ctr, aux, total;  // float offsets
 };
-__host__ __device__ inline Ro2Lds ro2_lds(int policy_total, int critic_total, int DP) {
+// Acrobot-v1's rings behind everything else (the other envs' layouts are unchanged): the state each observation slot was made
+// from ([slot][row]{th1, th2, dth1, dth2}), the env service's speculative step records ([step & 3][row][torque][16]: next
+// observation | next state) and the next episode's reset record of every row ([row][16], the same layout)
+constexpr int RO2_ACRO_REC = 16;
+__host__ __device__ constexpr int ro2_aux_floats(int env) {
+  return env == ORL_ENV_ACROBOT ? RO2_ORING * TILE_B * 4 + RO2_RING * TILE_B * 3 * RO2_ACRO_REC + TILE_B * RO2_ACRO_REC : 0;
+}
+__host__ __device__ inline Ro2Lds ro2_lds(int policy_total, int critic_total, int DP, int aux = 0) {
   Ro2Lds L;
   int o = policy_total;
   L.critic = o; o += critic_total;
@@ -67,6 +76,7 @@ __host__ __device__ inline Ro2Lds ro2_lds(int policy_total, int critic_total, in
   L.stage = o; o += RO2_RING * TILE_B * RO2_STG;
   L.gtab = o; o += 3 * 16;  // Gaussian heads: {std, 1 / (2 std^2), log std + log sqrt(2 pi)} per action dimension
   L.ctr = o; o += RC_WORDS;
+  L.aux = o; o += aux;
   L.total = o;
   return L;
 }
@@ -164,7 +174,7 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
   stage_tower(smem, A.ptheta, tlp, twp, false, threadIdx.x, blockDim.x, HMM, PSPLIT, true);
   stage_tower(smem + twp.total, A.ctheta, tlc, twc, false, threadIdx.x, blockDim.x, false, true, true);
   const int DP = KS > 0 ? 4 * KS : twp.DP;
-  const Ro2Lds L = ro2_lds(twp.total, twc.total, DP);
+  const Ro2Lds L = ro2_lds(twp.total, twc.total, DP, ro2_aux_floats(ENV));
   float* s_obs = smem + L.obs;
   unsigned* ctr = (unsigned*)(smem + L.ctr);
   unsigned* err = ctr + RC_ERR;
@@ -194,6 +204,28 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
     const int nn = n0 + threadIdx.x;
     s_pst[threadIdx.x] = nn < N ? A.r.env_state[(size_t)nn * PENDULUM_STATE_W + 0] : 0.f;
     s_pst[TILE_B + threadIdx.x] = nn < N ? A.r.env_state[(size_t)nn * PENDULUM_STATE_W + 1] : 0.f;
+  }
+  // Acrobot-v1 (ORL_ENV_ACROBOT): its step - RK4, four evaluations of the dynamics with their trigonometry and divisions - is
+  // about as long as a policy step and cannot start before the action is known.  So it is computed SPECULATIVELY: while the
+  // policy waves work on step t, the env service (wave 6) steps state t under all three torques (lane groups q = 0, 1, 2);
+  // wave 0 only selects the record of the sampled action, or the row's reset record when the episode ends.  The reset record
+  // (the next episode's first state and observation) only changes when an episode ends: lane group 3 redraws it in the step
+  // after a done, so on most steps the service wave's critical path is the RK4 alone.  The observation does not give the
+  // angles back bit for bit, so every observation slot carries its state (s_ast).  ORL_ACROBOT_SERIAL (a build-time A/B
+  // switch, never the shipped configuration) computes the step on wave 0 after sampling instead.
+  constexpr bool IS_ACRO = ENV == ORL_ENV_ACROBOT, IS_MCAR = ENV == ORL_ENV_MOUNTAINCAR;
+#ifdef ORL_ACROBOT_SERIAL
+  constexpr bool ACRO_SPEC = false;
+#else
+  constexpr bool ACRO_SPEC = true;
+#endif
+  float* s_ast = smem + L.aux;                          // [slot][16][4]
+  float* s_cand = s_ast + RO2_ORING * TILE_B * 4;       // [t & 3][16][3][RO2_ACRO_REC]
+  float* s_rrec = s_cand + RO2_RING * TILE_B * 3 * RO2_ACRO_REC;  // [16][RO2_ACRO_REC]
+  if (IS_ACRO && threadIdx.x < TILE_B) {
+    const int nn = n0 + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_ast[threadIdx.x * 4 + k] = nn < N ? A.r.env_state[(size_t)nn * ACROBOT_STATE_W + k] : 0.f;
   }
   if (IS_TTT && threadIdx.x < TILE_B) {
     const int jj = threadIdx.x, nn = n0 + jj;
@@ -285,7 +317,8 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
       smem[L.gtab + 32 + l] = ls + 0.91893853320467274178f;
     }
     // env state of the tile's rows (every lane of a row keeps a copy; lanes q == 0 write)
-    constexpr int SW = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : IS_TTT ? 0 : IS_PEND ? PENDULUM_STATE_W : CARTPOLE_STATE_W;  // (tic-tac-toe: bitboards below)
+    constexpr int SW = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : IS_TTT ? 0 : IS_PEND ? PENDULUM_STATE_W : IS_ACRO ? ACROBOT_STATE_W
+                       : IS_MCAR ? MOUNTAINCAR_STATE_W : CARTPOLE_STATE_W;  // (tic-tac-toe: bitboards below)
     float est[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float ep_ret = 0.f, ep_len = 0.f, fin_ret = 0.f, fin_cnt = 0.f;
     if (gw == 0 && ok) {
@@ -455,7 +488,9 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
         // slot (t + 1) & 7 of the observation ring held observation t - 7: the critic wave of step t - 7 has read it when its
         // flag says so; the staging / env rings (4 deep) are free once the store wave has finished step t - 4
         const int need_c = t - 6;
-        const bool ready = (int)fp[1] > t && (int)fp[2] > t && (int)fp[3] > t && (int)fs[0] > t && (int)fs[1] > t &&
+        // (Acrobot: the env service's records are needed only after sampling - waited for there, so that the head and the
+        // sampler overlap the speculative RK4)
+        const bool ready = (int)fp[1] > t && (int)fp[2] > t && (int)fp[3] > t && (int)fs[0] > t && (IS_ACRO || (int)fs[1] > t) &&
                            (int)fs[2] >= t - 3 && (int)fc[0] >= need_c && (int)fc[1] >= need_c && (int)fc[2] >= need_c;
         if (ready) break;
         if (spins > RO2_MAX_SPINS) { ro2_fail(err); break; }
@@ -626,6 +661,53 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
           s_pst[sl * 2 * TILE_B + j] = est[0];
           s_pst[sl * 2 * TILE_B + TILE_B + j] = est[1];
         }
+      } else if constexpr (IS_ACRO) {
+        // select: the sampled torque's record, or the reset record when the episode ends (env record: the three terminal flags)
+        const int a = discrete3_action(act0);
+        const int sl = (t + 1) & (RO2_ORING - 1);
+        bool term;
+        f32x4 rc;
+        for (unsigned spins = 0;; ++spins) {  // the service's counter and the terminal flags in one batch
+          const unsigned c = ro2_ld(ctr + RC_ENV);
+          envr0 = ro2_ld4f(er);
+          if ((int)c > t) break;
+          if (spins > RO2_MAX_SPINS) { ro2_fail(err); break; }
+        }
+        asm volatile("" ::: "memory");
+        if constexpr (ACRO_SPEC) {
+          term = (a == 0 ? envr0[0] : (a == 1 ? envr0[1] : envr0[2])) != 0.f;
+          rc = *(const f32x4*)(s_cand + (((t & 3) * TILE_B + j) * 3 + a) * RO2_ACRO_REC + 4 * (q < 3 ? q : 2));
+        } else {  // the A/B comparison: the whole step here, after sampling
+          const f32x4 sv = *(const f32x4*)(s_ast + ((t & (RO2_ORING - 1)) * TILE_B + j) * 4);
+          float s[4] = {sv[0], sv[1], sv[2], sv[3]}, o[6];
+          term = acrobot_step(s, a, o);
+          rc = q == 0 ? f32x4{o[0], o[1], o[2], o[3]} : (q == 1 ? f32x4{o[4], o[5], 0.f, 0.f} : f32x4{s[0], s[1], s[2], s[3]});
+        }
+        const float steps = est[4] + 1.f;
+        done = term || steps >= (float)A.r.episode_limit;
+        rew = term ? 0.f : -1.f;
+        est[4] = done ? 0.f : steps;
+        est[5] += done ? 1.f : 0.f;
+        // lane group q uses 4 floats of the record: 0 = observation 0..3, 1 = observation 4, 5 (and 2 zeros), 2 = the state
+        if (done) rc = *(const f32x4*)(s_rrec + j * RO2_ACRO_REC + 4 * (q < 3 ? q : 2));
+        float* nxt = s_obs + sl * TILE_B * DP + j * DP;
+        if (q == 0) *(f32x4*)nxt = ok ? rc : f32x4{0.f, 0.f, 0.f, 0.f};
+        else if (q == 1) *(f32x4*)(nxt + 4) = ok ? f32x4{rc[0], rc[1], 0.f, 0.f} : f32x4{0.f, 0.f, 0.f, 0.f};
+        else if (q == 2) *(f32x4*)(s_ast + (sl * TILE_B + j) * 4) = rc;
+      } else if constexpr (IS_MCAR) {
+        // the action's force, the clips, the left wall and the goal test; cos(3 p) and the reset state came from wave 6
+        // (env record: {gravity term, reset p, reset v})
+        float s[2] = {est[0], est[1]};
+        const bool term = mountaincar_post(s, envr0[0], discrete3_action(act0));
+        const float steps = est[2] + 1.f;
+        done = term || steps >= (float)A.r.episode_limit;
+        rew = -1.f;
+        est[2] = done ? 0.f : steps;
+        est[3] += done ? 1.f : 0.f;
+        est[0] = done ? envr0[1] : s[0];
+        est[1] = done ? envr0[2] : s[1];
+        float* nxt = s_obs + ((t + 1) & (RO2_ORING - 1)) * TILE_B * DP;
+        if (q == 0) *(f32x4*)(nxt + j * DP) = ok ? f32x4{est[0], est[1], 0.f, 0.f} : f32x4{0.f, 0.f, 0.f, 0.f};
       } else {
         CartPolePre cp;
         cp.costh = envr0[0]; cp.sinth = envr0[1]; cp.t1 = envr0[2]; cp.den = envr0[3];
@@ -653,6 +735,11 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
 #endif
     if (gw == 0) {
       const bool poisoned = ro2_ld(err) != 0u;
+      if constexpr (IS_ACRO) {  // the final state: what wave 0 published with the last observation
+        const f32x4 sv = *(const f32x4*)(s_ast + ((T & (RO2_ORING - 1)) * TILE_B + j) * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) est[k] = sv[k];
+      }
       if (q == 0 && ok) {
 #pragma unroll
         for (int k = 0; k < 8; ++k)
@@ -693,6 +780,8 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
     // ================================================================ the action-independent half of env.step =====
     float ep = (ENV == ORL_ENV_CARTPOLE && ok) ? A.r.env_state[(size_t)n * CARTPOLE_STATE_W + 5]
                : (IS_PEND && ok)                 ? A.r.env_state[(size_t)n * PENDULUM_STATE_W + 3]
+               : (IS_ACRO && ok)                 ? A.r.env_state[(size_t)n * ACROBOT_STATE_W + 5]
+               : (IS_MCAR && ok)                 ? A.r.env_state[(size_t)n * MOUNTAINCAR_STATE_W + 3]
                                                  : 0.f;
     for (int t = 0; t < T; ++t) {
       float* er = smem + L.env + ((t & 3) * TILE_B + j) * RO2_ENVW;
@@ -735,6 +824,43 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
           *(f32x4*)er = f32x4{pp.grav, pp.cost0, rs[0], rs[1]};
           *(f32x4*)(er + 4) = f32x4{ro[0], ro[1], 0.f, 0.f};
         }
+      } else if constexpr (IS_ACRO) {
+        // speculative step of state t (published with observation t): lane group q < 3 under action q; wave 0 selects one
+        // record after sampling.  Lane group 3 redraws the row's reset record after a done (and at the first step): the
+        // record of step t - 1's done was read by wave 0 before it published observation t, which this wave waited for.
+        // (Polling without sleeps: the RK4 is the step's longest path.  Its placement was measured not to matter - this wave
+        // at priority 0, 2 or 3, or wave 4 on wave 0's otherwise idle SIMD, all within 1.4 % - so it is latency, not issue
+        // slots, that sets the RK4's length.)
+        ro2_wait<false>(ctr + RC_OBS, t + 1, err);
+        const float dn = t >= 1 ? smem[L.stage + (((t - 1) & 3) * TILE_B + j) * RO2_STG + 33] : 1.f;  // done of step t - 1
+        if (t >= 1) ep += dn;
+        if (q == 3 && dn != 0.f) {
+          float s[4], o[6];
+          acrobot_reset(A.r.env_seed, (uint32_t)n, (uint32_t)(ep + 1.f), s);
+          acrobot_obs(s, o);
+          float* rec = s_rrec + j * RO2_ACRO_REC;
+          *(f32x4*)rec = f32x4{o[0], o[1], o[2], o[3]};
+          *(f32x4*)(rec + 4) = f32x4{o[4], o[5], 0.f, 0.f};
+          *(f32x4*)(rec + 8) = f32x4{s[0], s[1], s[2], s[3]};
+        }
+        if (ACRO_SPEC && q < 3) {
+          const f32x4 sv = *(const f32x4*)(s_ast + ((t & (RO2_ORING - 1)) * TILE_B + j) * 4);
+          float s[4] = {sv[0], sv[1], sv[2], sv[3]}, o[6];
+          const float tm = acrobot_step(s, q, o) ? 1.f : 0.f;
+          float* rec = s_cand + (((t & 3) * TILE_B + j) * 3 + q) * RO2_ACRO_REC;
+          *(f32x4*)rec = f32x4{o[0], o[1], o[2], o[3]};
+          *(f32x4*)(rec + 4) = f32x4{o[4], o[5], 0.f, 0.f};
+          *(f32x4*)(rec + 8) = f32x4{s[0], s[1], s[2], s[3]};
+          er[q] = tm;
+        }
+      } else if constexpr (IS_MCAR) {
+        // mountaincar_pre of state t (the observation is the state) and the next episode's reset state
+        ro2_wait(ctr + RC_OBS, t + 1, err);
+        if (t >= 1) ep += smem[L.stage + (((t - 1) & 3) * TILE_B + j) * RO2_STG + 33];  // done of step t - 1 (staged before obs t)
+        const float pre = mountaincar_pre(s_obs[(t & (RO2_ORING - 1)) * TILE_B * DP + j * DP]);
+        float rs[2];
+        mountaincar_reset(A.r.env_seed, (uint32_t)n, (uint32_t)(ep + 1.f), rs);
+        if (q == 0) *(f32x4*)er = f32x4{pre, rs[0], rs[1], 0.f};
       } else {
         ro2_wait(ctr + RC_OBS, t + 1, err);
         if (t >= 1) ep += smem[L.stage + (((t - 1) & 3) * TILE_B + j) * RO2_STG + 33];  // done of step t - 1 (staged before obs t)

@@ -8,7 +8,7 @@ batch_rewards(buffer), statistics(buffer), close()``.
 
 State lives in HBM; ``step`` launches ``orl_env_step``; the fused driver never calls ``step`` at all -
 it hands ``device_handle()`` to ``orl_rollout_fused`` which advances the same state in-kernel.
-Three kinds are built:
+Five kinds are built:
 
 * ``synthetic``: the fixed-step benchmark env - obs ~ N(0,1) keyed (seed, env, t), reward U(0,1),
   episodes of exactly ``episode_limit`` steps with per-env phase (env*7) mod limit, no bad transitions;
@@ -20,7 +20,16 @@ Three kinds are built:
   truncated at 200 steps with the same ``done`` / auto-reset semantics.  Reset states ``th ~ U(-pi, pi)``,
   ``thdot ~ U(-1, 1)`` come from the engine's own Philox stream keyed ``(seed, env, episode)``, as CartPole's do.
   One deviation from gymnasium's float64: ``th`` is wrapped back to ``[-pi, pi)`` after every step (csrc/orl_env.h) -
-  the same in real arithmetic, and it keeps the fp32 angle increment and ``sinf`` / ``cosf`` accurate.
+  the same in real arithmetic, and it keeps the fp32 angle increment and ``sinf`` / ``cosf`` accurate;
+* ``acrobot``: Acrobot-v1 (gymnasium classic_control/acrobot.py, book dynamics, one RK4 step of dt 0.2, fp32),
+  observation ``(cos th1, sin th1, cos th2, sin th2, dth1, dth2)`` in ``Box(-[1, 1, 1, 1, 4 pi, 9 pi], +[...])``,
+  ``Discrete(3)`` torques ``{-1, 0, +1}``, reward -1 per step and 0 on the terminating step, terminated when
+  ``-cos th1 - cos(th1 + th2) > 1``, truncated at 500 steps; the four state variables reset to ``U(-0.1, 0.1)``;
+* ``mountaincar``: MountainCar-v0 (gymnasium classic_control/mountain_car.py, fp32), observation ``(position,
+  velocity)`` in ``Box([-1.2, -0.07], [0.6, 0.07])``, ``Discrete(3)``, reward -1 per step, terminated at
+  ``position >= 0.5`` with ``velocity >= 0``, truncated at 200 steps; reset ``position ~ U(-0.6, -0.4)``, velocity 0.
+  Both reset from the engine's Philox stream keyed ``(seed, env, episode)``; their deviations from gymnasium (fp32,
+  ``cos(x - pi/2)`` written ``sin(x)``) are listed in csrc/orl_env.h and docs/beyond_config2.md.
 
 Env ``i`` is seeded ``seed + i*10086`` in the reference (sync_venv.py:136-137); here the counter-based
 generator is keyed by ``(seed, i)`` which gives every lane its own stream the same way.
@@ -37,11 +46,19 @@ from ... import _native as nat
 from ... import ops, spaces
 
 
+# (low, high) of the classic-control envs whose observation space is a bounded Box (gymnasium's values)
+OBSERVATION_BOUNDS = {
+    "acrobot": ([-1.0, -1.0, -1.0, -1.0, -4.0 * np.pi, -9.0 * np.pi], [1.0, 1.0, 1.0, 1.0, 4.0 * np.pi, 9.0 * np.pi]),
+    "mountaincar": ([-1.2, -0.07], [0.6, 0.07]),
+}
+
+
 class DeviceVecEnv:
     def __init__(self, kind: str, env_num: int, obs_dim: int, action_space, env_name: str, episode_limit: int,
                  device="cuda:0", seed: int = 0):
         self.kind = kind
-        self.env_kind = {"synthetic": ops.ENV_SYNTH, "cartpole": ops.ENV_CARTPOLE, "pendulum": ops.ENV_PENDULUM}[kind]
+        self.env_kind = {"synthetic": ops.ENV_SYNTH, "cartpole": ops.ENV_CARTPOLE, "pendulum": ops.ENV_PENDULUM,
+                         "acrobot": ops.ENV_ACROBOT, "mountaincar": ops.ENV_MOUNTAINCAR}[kind]
         self.device = nat.require_gpu(device)
         self._n = int(env_num)
         self._obs_dim = int(obs_dim)
@@ -49,6 +66,10 @@ class DeviceVecEnv:
         if kind == "pendulum":
             self._observation_space = spaces.Box(np.array([-1.0, -1.0, -8.0], np.float32),
                                                  np.array([1.0, 1.0, 8.0], np.float32), (obs_dim,), np.float32)
+        elif kind in OBSERVATION_BOUNDS:
+            lo, hi = OBSERVATION_BOUNDS[kind]
+            self._observation_space = spaces.Box(np.array(lo, np.float32), np.array(hi, np.float32), (obs_dim,),
+                                                 np.float32)
         else:
             self._observation_space = spaces.Box(-np.inf, np.inf, (obs_dim,), np.float32)
         self._env_name = env_name
