@@ -1,5 +1,6 @@
-"""End-to-end PPO iterations on the device classic-control envs with a Discrete(3) head, default recipe (ppo_epoch 10,
-num_mini_batch 1, hidden 64), fused chain rollout: Acrobot-v1 at 4096 envs x 500 and MountainCar-v0 at 4096 envs x 200.
+"""End-to-end PPO iterations on the device classic-control envs, default recipe (ppo_epoch 10, num_mini_batch 1, hidden
+64), fused chain rollout: Acrobot-v1 at 4096 envs x 500 and MountainCar-v0 at 4096 envs x 200 with a Discrete(3) head,
+MountainCarContinuous-v0 at 4096 envs x 200 with a Box(1) Gaussian head.
 Stand-alone (bench.py does not run it); one JSON line per env:
 
     python benchmarks/classic_control.py [--steps 3 --warmup 2]
@@ -17,6 +18,8 @@ CONFIGS = [
          envs=4096, T=500, agents=1, env_kw={}, argv=[]),
     dict(name="MountainCar-v0, PPO, 4096 envs x 200, obs 2, Discrete(3), device env, fused rollout", env="MountainCar-v0",
          envs=4096, T=200, agents=1, env_kw={}, argv=[]),
+    dict(name="MountainCarContinuous-v0, PPO, 4096 envs x 200, obs 2, Box(1), device env, fused rollout",
+         env="MountainCarContinuous-v0", envs=4096, T=200, agents=1, env_kw={}, argv=[]),
 ]
 
 

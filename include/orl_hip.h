@@ -428,6 +428,10 @@ int orl_minibatch_moments(const float* records, int rec_width, int ret_col, cons
 #define ORL_ENV_MOUNTAINCAR 7 /* MountainCar-v0 dynamics (gymnasium classic_control mountain_car.py, fp32): obs 2 (position,
                                * velocity), Discrete(3), reward -1.  Fused rollout: the chain kernel only (Discrete(3), obs_dim 2;
                                * opp_reserved 1 is rejected) */
+#define ORL_ENV_MOUNTAINCAR_CONT 8 /* MountainCarContinuous-v0 dynamics (gymnasium classic_control continuous_mountain_car.py,
+                                    * fp32): obs 2 (position, velocity), Box(-1, 1, (1,)) float force, reward -0.1 a^2 on the
+                                    * unclipped action + 100 on the terminal step.  Fused rollout: the chain kernel only
+                                    * (Gaussian head, n_out 1, obs_dim 2; opp_reserved 1 is rejected) */
 
 typedef struct orl_rollout_args {
   orl_buffer_ptrs buf;
@@ -445,7 +449,7 @@ typedef struct orl_rollout_args {
   const float* opp_thetas; /* parameters of policy g at opp_thetas + g*opp_theta_stride */
   int64_t opp_theta_stride;
   int32_t opp_group_rows;  /* envs [g*opp_group_rows, ...) play policy g; a multiple of 16 */
-  int32_t opp_reserved;    /* ORL_ENV_SYNTH / ORL_ENV_CARTPOLE / ORL_ENV_TTT / ORL_ENV_PENDULUM / ORL_ENV_ACROBOT / ORL_ENV_MOUNTAINCAR: 0 = the round-6 chain rollout (policy-only step chain, the
+  int32_t opp_reserved;    /* ORL_ENV_SYNTH / ORL_ENV_CARTPOLE / ORL_ENV_TTT / ORL_ENV_PENDULUM / ORL_ENV_ACROBOT / ORL_ENV_MOUNTAINCAR / ORL_ENV_MOUNTAINCAR_CONT: 0 = the round-6 chain rollout (policy-only step chain, the
                             * critic on background waves of the same launch), 1 = the round-5 kernel (both towers in the
                             * step loop).  Ignored by the tic-tac-toe POOL envs (always the round-5 kernel). */
   uint64_t opp_seed;       /* Philox seed of the opponents' sampling; counter = (env, opp_rng_step0 + t) */

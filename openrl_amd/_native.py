@@ -19,6 +19,7 @@ ORL_HEAD_VALUE, ORL_HEAD_CATEGORICAL, ORL_HEAD_GAUSSIAN = 0, 1, 2
 ORL_ENV_SYNTH, ORL_ENV_CARTPOLE, ORL_ENV_TTT, ORL_ENV_TTT_POOL, ORL_ENV_MPE_SPREAD = 0, 1, 2, 3, 4
 ORL_ENV_PENDULUM = 5
 ORL_ENV_ACROBOT, ORL_ENV_MOUNTAINCAR = 6, 7
+ORL_ENV_MOUNTAINCAR_CONT = 8
 ORL_GATHER_MAX = 12
 ORL_IPC_HANDLE_BYTES = 64
 ORL_VERSION = 306  # must equal include/orl_hip.h; checked against the loaded library

@@ -2,7 +2,7 @@
 //   orl_act_step      : K1-K4 fused policy + value forward and action sampling for B rows
 //   orl_rollout_fused : T steps of {forward, sample, env.step, buffer insert} in ONE launch for
 //                       device-resident batched envs (synthetic fixed-step env, CartPole-v1, Pendulum-v1, Acrobot-v1,
-//                       MountainCar-v0)
+//                       MountainCar-v0, MountainCarContinuous-v0)
 //   orl_env_reset     : initial env state + first observation
 //
 // Geometry: one workgroup owns one 16-row tile (fp32 MFMA 16x16x4, see orl_mlp.h).  orl_act_step uses 2
@@ -178,6 +178,12 @@ __global__ __launch_bounds__(256) void env_reset_kernel(float* __restrict__ env_
     float* st = env_state + (size_t)n * MOUNTAINCAR_STATE_W;
     float s[2];
     mountaincar_reset(seed, (uint32_t)n, 0u, s);
+    st[0] = s[0]; st[1] = s[1]; st[2] = 0.f; st[3] = 0.f;
+    obs0[(size_t)n * 2 + 0] = s[0]; obs0[(size_t)n * 2 + 1] = s[1];
+  } else if (ENV == ORL_ENV_MOUNTAINCAR_CONT) {
+    float* st = env_state + (size_t)n * MOUNTAINCAR_CONT_STATE_W;
+    float s[2];
+    mountaincar_cont_reset(seed, (uint32_t)n, 0u, s);
     st[0] = s[0]; st[1] = s[1]; st[2] = 0.f; st[3] = 0.f;
     obs0[(size_t)n * 2 + 0] = s[0]; obs0[(size_t)n * 2 + 1] = s[1];
   } else {
@@ -1245,6 +1251,7 @@ int orl_env_state_width(int env_kind) {
   if (env_kind == ORL_ENV_PENDULUM) return PENDULUM_STATE_W;
   if (env_kind == ORL_ENV_ACROBOT) return ACROBOT_STATE_W;
   if (env_kind == ORL_ENV_MOUNTAINCAR) return MOUNTAINCAR_STATE_W;
+  if (env_kind == ORL_ENV_MOUNTAINCAR_CONT) return MOUNTAINCAR_CONT_STATE_W;
   return fail(ORL_E_INVALID, "orl_env_state_width: unknown env kind %d", env_kind);
 }
 
@@ -1270,6 +1277,10 @@ int orl_env_reset(int env_kind, float* env_state, float* ep_stats, float* obs0, 
   } else if (env_kind == ORL_ENV_MOUNTAINCAR) {
     ORL_REQUIRE(obs_dim == 2, "orl_env_reset: MountainCar obs_dim must be 2");
     hipLaunchKernelGGL((env_reset_kernel<ORL_ENV_MOUNTAINCAR>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                       env_state, ep_stats, obs0, N, obs_dim, env_seed, episode_limit);
+  } else if (env_kind == ORL_ENV_MOUNTAINCAR_CONT) {
+    ORL_REQUIRE(obs_dim == 2, "orl_env_reset: MountainCarContinuous obs_dim must be 2");
+    hipLaunchKernelGGL((env_reset_kernel<ORL_ENV_MOUNTAINCAR_CONT>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
                        env_state, ep_stats, obs0, N, obs_dim, env_seed, episode_limit);
   } else {
     return fail(ORL_E_INVALID, "orl_env_reset: unknown env kind %d", env_kind);
@@ -1317,6 +1328,13 @@ int orl_env_step_dev(int env_kind, float* env_state, float* ep_stats, const floa
                 "orl_env_step: MountainCar needs actions and 2-d obs (got width %d, obs_dim %d)", action_width, obs_dim);
     hipLaunchKernelGGL((env_step_kernel<ORL_ENV_MOUNTAINCAR>), dim3(grid), dim3(256), 0, (hipStream_t)stream, env_state,
                        ep_stats, actions, action_width, obs, rewards, dones, N, obs_dim, env_seed, episode_limit,
+                       global_step, (const long long*)global_step_dev);
+  } else if (env_kind == ORL_ENV_MOUNTAINCAR_CONT) {
+    ORL_REQUIRE(actions && action_width == 1 && obs_dim == 2,
+                "orl_env_step: MountainCarContinuous needs float actions of width 1 and 2-d obs (got width %d, obs_dim %d)",
+                action_width, obs_dim);
+    hipLaunchKernelGGL((env_step_kernel<ORL_ENV_MOUNTAINCAR_CONT>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                       env_state, ep_stats, actions, action_width, obs, rewards, dones, N, obs_dim, env_seed, episode_limit,
                        global_step, (const long long*)global_step_dev);
   } else {
     return fail(ORL_E_INVALID, "orl_env_step: unknown env kind %d", env_kind);
@@ -1395,6 +1413,15 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
                 "orl_rollout_fused: %s runs on the chain kernel only - opp_reserved = 1 (amd_rollout_kernel=lockstep) "
                 "selects the round-5 lock-step kernel, which is not built for it", nm);
   }
+  const bool mcc = args->env_kind == ORL_ENV_MOUNTAINCAR_CONT;
+  if (mcc) {
+    ORL_REQUIRE(pnet->head_kind == ORL_HEAD_GAUSSIAN && pnet->n_out == 1 && b.Dp == 2,
+                "orl_rollout_fused: MountainCarContinuous needs a Gaussian head with n_out 1 and 2-d obs (got head %d, n_out %d, "
+                "obs %d)", pnet->head_kind, pnet->n_out, b.Dp);
+    ORL_REQUIRE(args->opp_reserved != 1,
+                "orl_rollout_fused: MountainCarContinuous runs on the chain kernel only - opp_reserved = 1 "
+                "(amd_rollout_kernel=lockstep) selects the round-5 lock-step kernel, which is not built for it");
+  }
   const bool pool = args->env_kind == ORL_ENV_TTT_POOL;
   const bool perk = pool && args->opp_per_reset != 0;  // per-env opponents, re-drawn in-kernel at every auto-reset
   if (pool)
@@ -1440,11 +1467,11 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
   // registers of 4 columns each.  Wider observations (and towers whose rings do not fit beside both images, from obs 65
   // with more than 2 outputs) keep the round-5 kernel, whose fc1 loops over every k-step.
   // (Pendulum's towers - obs 3, one output - are far below the LDS limit: the fallback below never has to take it)
-  if ((pend || acro || mcar) && lds2 > 160 * 1024)
+  if ((pend || acro || mcar || mcc) && lds2 > 160 * 1024)
     return fail(ORL_E_INVALID, "orl_rollout_fused: env kind %d's chain kernel needs %zu B of LDS (> 160 KiB)", args->env_kind,
                 lds2);
   if ((args->env_kind == ORL_ENV_SYNTH || args->env_kind == ORL_ENV_CARTPOLE || args->env_kind == ORL_ENV_TTT || pend || acro ||
-       mcar) &&
+       mcar || mcc) &&
       args->opp_reserved != 1 && twp.DP <= 64 && lds2 <= 160 * 1024) {
 #define ORL_RO2_LAUNCH3(NO, HD, EV, KS)                                                                               \
   do {                                                                                                               \
@@ -1461,6 +1488,8 @@ int orl_rollout_fused(const orl_net_desc* pnet, const float* ptheta, const orl_n
       ORL_RO2_LAUNCH3(8, ORL_HEAD_CATEGORICAL, ORL_ENV_ACROBOT, 2);  // the wide 3-class head, fc1's two k-steps at compile time
     } else if (mcar) {
       ORL_RO2_LAUNCH3(8, ORL_HEAD_CATEGORICAL, ORL_ENV_MOUNTAINCAR, 1);
+    } else if (mcc) {
+      ORL_RO2_LAUNCH3(2, ORL_HEAD_GAUSSIAN, ORL_ENV_MOUNTAINCAR_CONT, 1);  // Pendulum's narrow Gaussian head
     } else if (args->env_kind == ORL_ENV_TTT) {
       ORL_RO2_LAUNCH3(16, ORL_HEAD_CATEGORICAL, ORL_ENV_TTT, 0);  // the random opponent (the pool variants keep the round-5 kernel)
     } else if (twp.DP == 4 && pnet->head_kind == ORL_HEAD_CATEGORICAL && pnet->n_out <= 2) {

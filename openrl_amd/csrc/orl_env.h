@@ -1,5 +1,5 @@
 // orl_env.h - the device-resident single-agent envs (synthetic fixed-step env of SURVEY.md section 8d, CartPole-v1,
-// Pendulum-v1, Acrobot-v1, MountainCar-v0) as per-env device functions, shared by the fused rollout kernels (orl_act.hip: default towers,
+// Pendulum-v1, Acrobot-v1, MountainCar-v0, MountainCarContinuous-v0) as per-env device functions, shared by the fused rollout kernels (orl_act.hip: default towers,
 // orl_gen_fused.hip: general towers) and the stand-alone env kernels: one definition, so every route steps an env with the same arithmetic and the
 // same Philox streams.  Not part of the C ABI.
 #pragma once
@@ -127,7 +127,8 @@ __device__ inline void pendulum_obs(const float (&s)[2], float* __restrict__ obs
 }
 
 // --------------------------------------------------------------------------------------------------
-// Acrobot-v1 and MountainCar-v0 (gymnasium classic_control acrobot.py / mountain_car.py) in fp32, Discrete(3) actions.
+// Acrobot-v1, MountainCar-v0 and MountainCarContinuous-v0 (gymnasium classic_control acrobot.py / mountain_car.py /
+// continuous_mountain_car.py) in fp32: Discrete(3) actions, MountainCarContinuous a Box(-1, 1, (1,)) force.
 //
 // Written for reproducible arithmetic in translation units built with -ffast-math (orl_act.hip): the functions below turn
 // off reassociation and implicit contraction (ORL_CC_FP_EXACT - every fused multiply-add is an explicit fmaf), and the
@@ -140,9 +141,13 @@ __device__ inline void pendulum_obs(const float (&s)[2], float* __restrict__ obs
 //   * fp32 instead of float64 (gymnasium's np.append promotes the state to float64);
 //   * cos(x - pi/2) is written as sin(x) (equal in real arithmetic), and the unit masses / lengths / inertias are folded
 //     into the constants of _dsdt (d1 = 3.5 + cos th2, d2 = 1.25 + 0.5 cos th2, d2^2 / d1 = d2 (d2 / d1)).
+// And one for MountainCarContinuous:
+//   * fp32 instead of float64 for the step and the reward (gymnasium steps in float64 and rounds the state to float32
+//     after every step, so only the step's intermediate values and the reward differ).
 // The wrap of th1 / th2 into [-pi, pi] is gymnasium's while loop, bounded at 16 turns each way: the states reachable in a
 // step (|th| <= pi + dt |dth| with the bounded speeds and RK4's intermediate ones) never need more than a few.
-// Reset states come from the engine's own Philox stream keyed (seed, env, episode), as CartPole's do.
+// Reset states come from the engine's own Philox stream keyed (seed, env, episode), as CartPole's do (each env under its
+// own key).
 // --------------------------------------------------------------------------------------------------
 constexpr int ACROBOT_STATE_W = 6;      // {th1, th2, dth1, dth2, steps_in_episode, episodes}
 constexpr int MOUNTAINCAR_STATE_W = 4;  // {position, velocity, steps_in_episode, episodes}
@@ -248,6 +253,33 @@ __device__ inline bool mountaincar_post(float (&s)[2], float pre, int a) {
   s[0] = p; s[1] = v;
   return p >= 0.5f && v >= 0.0f;
 }
+// MountainCarContinuous-v0 (gymnasium classic_control continuous_mountain_car.py): the same car and hill, a Box(-1, 1, (1,))
+// force of power 0.0015, the goal at 0.45 (not MountainCar-v0's 0.5), reward -0.1 a^2 on every step plus 100 on the terminal
+// one - charged on the UNCLIPPED action a (gymnasium's math.pow(action[0], 2)), while the dynamics use the clipped force.
+// The gravity term is mountaincar_pre's.  The deviations are those listed above (fp32, the accurate cos, the Philox resets).
+constexpr int MOUNTAINCAR_CONT_STATE_W = 4;  // {position, velocity, steps_in_episode, episodes}
+__device__ inline void mountaincar_cont_reset(uint64_t seed, uint32_t env, uint32_t episode, float (&s)[2]) {
+  ORL_CC_FP_EXACT
+  const u4 r = philox4x32_10(seed, env, 0x3CC40000u, episode, 0u);
+  s[0] = fmaf(u01(r.x), 0.2f, -0.6f);
+  s[1] = 0.0f;
+}
+// s = {p, v} in / out, pre = mountaincar_pre(p), action unclipped; returns whether the new state is terminal
+__device__ inline bool mountaincar_cont_post(float (&s)[2], float pre, float action) {
+  ORL_CC_FP_EXACT
+  const float force = fminf(fmaxf(action, -1.0f), 1.0f);
+  float v = s[1] + fmaf(force, 0.0015f, pre);
+  v = fminf(fmaxf(v, -0.07f), 0.07f);
+  float p = s[0] + v;
+  p = fminf(fmaxf(p, -1.2f), 0.6f);
+  if (p == -1.2f && v < 0.0f) v = 0.0f;
+  s[0] = p; s[1] = v;
+  return p >= 0.45f && v >= 0.0f;
+}
+__device__ inline float mountaincar_cont_reward(bool term, float action) {
+  ORL_CC_FP_EXACT
+  return (term ? 100.0f : 0.0f) - (action * action) * 0.1f;
+}
 // actions of the Discrete(3) envs as a class index: the float action is truncated and clamped into {0, 1, 2}
 __device__ inline int discrete3_action(float action) {
   const int a = (int)action;
@@ -314,6 +346,19 @@ __device__ inline void env_step_state(float* __restrict__ st, float* __restrict_
     }
     st[0] = s[0]; st[1] = s[1];
     obs_out[0] = s[0]; obs_out[1] = s[1];
+  } else if (ENV == ORL_ENV_MOUNTAINCAR_CONT) {
+    float s[2] = {st[0], st[1]};
+    const bool term = mountaincar_cont_post(s, mountaincar_pre(s[0]), action);
+    r = mountaincar_cont_reward(term, action);
+    const float steps = st[2] + 1.f;
+    d = term || steps >= (float)episode_limit;
+    st[2] = d ? 0.f : steps;
+    if (d) {
+      st[3] += 1.f;
+      mountaincar_cont_reset(seed, (uint32_t)n, (uint32_t)st[3], s);
+    }
+    st[0] = s[0]; st[1] = s[1];
+    obs_out[0] = s[0]; obs_out[1] = s[1];
   } else {
     float s[4] = {st[0], st[1], st[2], st[3]};
     const bool term = cartpole_step(s, (int)action);
@@ -342,6 +387,7 @@ __device__ inline void env_step_one(float* __restrict__ env_state, float* __rest
                     : ENV == ORL_ENV_PENDULUM    ? PENDULUM_STATE_W
                     : ENV == ORL_ENV_ACROBOT     ? ACROBOT_STATE_W
                     : ENV == ORL_ENV_MOUNTAINCAR ? MOUNTAINCAR_STATE_W
+                    : ENV == ORL_ENV_MOUNTAINCAR_CONT ? MOUNTAINCAR_CONT_STATE_W
                                                  : CARTPOLE_STATE_W;
   env_step_state<ENV>(env_state + (size_t)n * W, ep_stats != nullptr ? ep_stats + (size_t)n * 4 : nullptr, n, D, seed,
                       episode_limit, tg, action, obs_out, r, d);

@@ -1,5 +1,5 @@
 // orl_rollout2.h - round 6: the fused rollout of the single-agent device envs (synthetic fixed-step env, CartPole-v1, tic-tac-toe
-// vs the random opponent, Pendulum-v1, Acrobot-v1, MountainCar-v0) as ONE dependent chain per 16-env tile with everything else taken off it (included by orl_act.hip, inside namespace orl).
+// vs the random opponent, Pendulum-v1, Acrobot-v1, MountainCar-v0, MountainCarContinuous-v0) as ONE dependent chain per 16-env tile with everything else taken off it (included by orl_act.hip, inside namespace orl).
 //
 // What the round-5 kernel (rollout_kernel, still built: tic-tac-toe runs on it, args.opp_reserved = 1 selects it for A/B) did
 // per step: policy AND critic tower in lock step on the same four SIMDs (an fp32 MFMA occupies the SIMD's VALU datapath, so the
@@ -28,7 +28,7 @@
 //     ahead, wave 6 the action-independent half of the env step (synthetic: reward + next observation; CartPole: cos / sin of
 //     the pole angle and the reset state of the next episode - cartpole_pre / cartpole_reset; Pendulum: the gravity term, the
 //     action-independent cost and the next episode's reset state with its observation - pendulum_pre / pendulum_reset;
-//     MountainCar: the gravity term cos(3 p) and the reset state; Acrobot: the WHOLE step under each of the three torques and,
+//     MountainCar / MountainCarContinuous: the gravity term cos(3 p) and the reset state; Acrobot: the WHOLE step under each of the three torques and,
 //     after a done, the reset record - wave 0 selects the sampled one), wave 7
 //     writes the step's rows of
 //     the rollout buffer (coalesced: the 16 rows of a field are contiguous) from an LDS staging ring.  Waves 4 and 8 exit: they
@@ -214,6 +214,7 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
   // angles back bit for bit, so every observation slot carries its state (s_ast).  ORL_ACROBOT_SERIAL (a build-time A/B
   // switch, never the shipped configuration) computes the step on wave 0 after sampling instead.
   constexpr bool IS_ACRO = ENV == ORL_ENV_ACROBOT, IS_MCAR = ENV == ORL_ENV_MOUNTAINCAR;
+  constexpr bool IS_MCC = ENV == ORL_ENV_MOUNTAINCAR_CONT;
 #ifdef ORL_ACROBOT_SERIAL
   constexpr bool ACRO_SPEC = false;
 #else
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
     }
     // env state of the tile's rows (every lane of a row keeps a copy; lanes q == 0 write)
     constexpr int SW = ENV == ORL_ENV_SYNTH ? SYNTH_STATE_W : IS_TTT ? 0 : IS_PEND ? PENDULUM_STATE_W : IS_ACRO ? ACROBOT_STATE_W
-                       : IS_MCAR ? MOUNTAINCAR_STATE_W : CARTPOLE_STATE_W;  // (tic-tac-toe: bitboards below)
+                       : IS_MCAR ? MOUNTAINCAR_STATE_W : IS_MCC ? MOUNTAINCAR_CONT_STATE_W : CARTPOLE_STATE_W;  // (tic-tac-toe: bitboards below)
     float est[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float ep_ret = 0.f, ep_len = 0.f, fin_ret = 0.f, fin_cnt = 0.f;
     if (gw == 0 && ok) {
@@ -694,14 +695,21 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
         if (q == 0) *(f32x4*)nxt = ok ? rc : f32x4{0.f, 0.f, 0.f, 0.f};
         else if (q == 1) *(f32x4*)(nxt + 4) = ok ? f32x4{rc[0], rc[1], 0.f, 0.f} : f32x4{0.f, 0.f, 0.f, 0.f};
         else if (q == 2) *(f32x4*)(s_ast + (sl * TILE_B + j) * 4) = rc;
-      } else if constexpr (IS_MCAR) {
+      } else if constexpr (IS_MCAR || IS_MCC) {
         // the action's force, the clips, the left wall and the goal test; cos(3 p) and the reset state came from wave 6
-        // (env record: {gravity term, reset p, reset v})
+        // (env record: {gravity term, reset p, reset v}).  MountainCarContinuous clips the force and charges its reward on
+        // the raw sample act0.
         float s[2] = {est[0], est[1]};
-        const bool term = mountaincar_post(s, envr0[0], discrete3_action(act0));
+        bool term;
+        if constexpr (IS_MCC) {
+          term = mountaincar_cont_post(s, envr0[0], act0);
+          rew = mountaincar_cont_reward(term, act0);
+        } else {
+          term = mountaincar_post(s, envr0[0], discrete3_action(act0));
+          rew = -1.f;
+        }
         const float steps = est[2] + 1.f;
         done = term || steps >= (float)A.r.episode_limit;
-        rew = -1.f;
         est[2] = done ? 0.f : steps;
         est[3] += done ? 1.f : 0.f;
         est[0] = done ? envr0[1] : s[0];
@@ -782,6 +790,7 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
                : (IS_PEND && ok)                 ? A.r.env_state[(size_t)n * PENDULUM_STATE_W + 3]
                : (IS_ACRO && ok)                 ? A.r.env_state[(size_t)n * ACROBOT_STATE_W + 5]
                : (IS_MCAR && ok)                 ? A.r.env_state[(size_t)n * MOUNTAINCAR_STATE_W + 3]
+               : (IS_MCC && ok)                  ? A.r.env_state[(size_t)n * MOUNTAINCAR_CONT_STATE_W + 3]
                                                  : 0.f;
     for (int t = 0; t < T; ++t) {
       float* er = smem + L.env + ((t & 3) * TILE_B + j) * RO2_ENVW;
@@ -853,13 +862,14 @@ __global__ __launch_bounds__(RO2_THREADS) void rollout2_kernel(RolloutArgs A) {
           *(f32x4*)(rec + 8) = f32x4{s[0], s[1], s[2], s[3]};
           er[q] = tm;
         }
-      } else if constexpr (IS_MCAR) {
+      } else if constexpr (IS_MCAR || IS_MCC) {
         // mountaincar_pre of state t (the observation is the state) and the next episode's reset state
         ro2_wait(ctr + RC_OBS, t + 1, err);
         if (t >= 1) ep += smem[L.stage + (((t - 1) & 3) * TILE_B + j) * RO2_STG + 33];  // done of step t - 1 (staged before obs t)
         const float pre = mountaincar_pre(s_obs[(t & (RO2_ORING - 1)) * TILE_B * DP + j * DP]);
         float rs[2];
-        mountaincar_reset(A.r.env_seed, (uint32_t)n, (uint32_t)(ep + 1.f), rs);
+        if constexpr (IS_MCC) mountaincar_cont_reset(A.r.env_seed, (uint32_t)n, (uint32_t)(ep + 1.f), rs);
+        else mountaincar_reset(A.r.env_seed, (uint32_t)n, (uint32_t)(ep + 1.f), rs);
         if (q == 0) *(f32x4*)er = f32x4{pre, rs[0], rs[1], 0.f};
       } else {
         ro2_wait(ctr + RC_OBS, t + 1, err);

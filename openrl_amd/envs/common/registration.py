@@ -22,8 +22,8 @@ def make(id: str, env_num: int = 1, asynchronous: bool = False, add_monitor: boo
          render_mode: Optional[str] = None, make_custom_envs: Optional[Callable] = None, auto_reset: bool = True,
          **kwargs):
     """Same signature as the reference.  Extra keyword arguments understood here: ``device`` (default
-    "cuda:0"), ``seed``, ``episode_limit`` (CartPole-v1: 500, Pendulum-v1: 200, Acrobot-v1: 500, MountainCar-v0: 200), and
-    for the synthetic env ``obs_dim``,
+    "cuda:0"), ``seed``, ``episode_limit`` (CartPole-v1: 500, Pendulum-v1: 200, Acrobot-v1: 500, MountainCar-v0: 200,
+    MountainCarContinuous-v0: 999), and for the synthetic env ``obs_dim``,
     ``action_space``."""
     device = kwargs.pop("device", "cuda:0")
     seed = kwargs.pop("seed", 0)
@@ -41,6 +41,9 @@ def make(id: str, env_num: int = 1, asynchronous: bool = False, add_monitor: boo
     if id == "MountainCar-v0":  # gymnasium classic_control, max_episode_steps=200
         return DeviceVecEnv("mountaincar", env_num, 2, spaces.Discrete(3), id, kwargs.pop("episode_limit", 200),
                             device=device, seed=seed)
+    if id == "MountainCarContinuous-v0":  # gymnasium classic_control, max_episode_steps=999
+        return DeviceVecEnv("mountaincar_continuous", env_num, 2, spaces.Box(-1.0, 1.0, (1,), np.float32), id,
+                            kwargs.pop("episode_limit", 999), device=device, seed=seed)
     if id.startswith(_SYNTH_PREFIX):
         obs_dim = kwargs.pop("obs_dim", 4)
         act = kwargs.pop("action_space", spaces.Discrete(2))
@@ -71,6 +74,6 @@ def make(id: str, env_num: int = 1, asynchronous: bool = False, add_monitor: boo
                                            opponent_strategy=kwargs.pop("opponent_strategy", "RandomOpponent"))
         return TicTacToeVecEnv(env_num, id, device=device, seed=seed)
     raise NotImplementedError(
-        "env id %r is not a device-resident env of the MI355X engine (built: 'CartPole-v1', 'Pendulum-v1', 'Acrobot-v1', 'MountainCar-v0', 'simple_spread', 'tictactoe_v3', '%s-v0'); "
+        "env id %r is not a device-resident env of the MI355X engine (built: 'CartPole-v1', 'Pendulum-v1', 'Acrobot-v1', 'MountainCar-v0', 'MountainCarContinuous-v0', 'simple_spread', 'tictactoe_v3', '%s-v0'); "
         "pass make_custom_envs=... returning a duck-typed VecEnv (gymnasium is not part of this engine)"
         % (id, _SYNTH_PREFIX))

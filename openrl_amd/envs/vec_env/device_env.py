@@ -8,7 +8,7 @@ batch_rewards(buffer), statistics(buffer), close()``.
 
 State lives in HBM; ``step`` launches ``orl_env_step``; the fused driver never calls ``step`` at all -
 it hands ``device_handle()`` to ``orl_rollout_fused`` which advances the same state in-kernel.
-Five kinds are built:
+Six kinds are built:
 
 * ``synthetic``: the fixed-step benchmark env - obs ~ N(0,1) keyed (seed, env, t), reward U(0,1),
   episodes of exactly ``episode_limit`` steps with per-env phase (env*7) mod limit, no bad transitions;
@@ -29,7 +29,11 @@ Five kinds are built:
   velocity)`` in ``Box([-1.2, -0.07], [0.6, 0.07])``, ``Discrete(3)``, reward -1 per step, terminated at
   ``position >= 0.5`` with ``velocity >= 0``, truncated at 200 steps; reset ``position ~ U(-0.6, -0.4)``, velocity 0.
   Both reset from the engine's Philox stream keyed ``(seed, env, episode)``; their deviations from gymnasium (fp32,
-  ``cos(x - pi/2)`` written ``sin(x)``) are listed in csrc/orl_env.h and docs/beyond_config2.md.
+  ``cos(x - pi/2)`` written ``sin(x)``) are listed in csrc/orl_env.h and docs/beyond_config2.md;
+* ``mountaincar_continuous``: MountainCarContinuous-v0 (gymnasium classic_control/continuous_mountain_car.py, fp32), the
+  same observation and reset as ``mountaincar``, a ``Box(-1, 1, (1,))`` force (clipped, power 0.0015), reward
+  ``-0.1 a**2`` on the unclipped action plus 100 on the terminating step, terminated at ``position >= 0.45`` with
+  ``velocity >= 0``, truncated at 999 steps; its reset stream has a key of its own.
 
 Env ``i`` is seeded ``seed + i*10086`` in the reference (sync_venv.py:136-137); here the counter-based
 generator is keyed by ``(seed, i)`` which gives every lane its own stream the same way.
@@ -50,6 +54,7 @@ from ... import ops, spaces
 OBSERVATION_BOUNDS = {
     "acrobot": ([-1.0, -1.0, -1.0, -1.0, -4.0 * np.pi, -9.0 * np.pi], [1.0, 1.0, 1.0, 1.0, 4.0 * np.pi, 9.0 * np.pi]),
     "mountaincar": ([-1.2, -0.07], [0.6, 0.07]),
+    "mountaincar_continuous": ([-1.2, -0.07], [0.6, 0.07]),
 }
 
 
@@ -58,7 +63,8 @@ class DeviceVecEnv:
                  device="cuda:0", seed: int = 0):
         self.kind = kind
         self.env_kind = {"synthetic": ops.ENV_SYNTH, "cartpole": ops.ENV_CARTPOLE, "pendulum": ops.ENV_PENDULUM,
-                         "acrobot": ops.ENV_ACROBOT, "mountaincar": ops.ENV_MOUNTAINCAR}[kind]
+                         "acrobot": ops.ENV_ACROBOT, "mountaincar": ops.ENV_MOUNTAINCAR,
+                         "mountaincar_continuous": ops.ENV_MOUNTAINCAR_CONT}[kind]
         self.device = nat.require_gpu(device)
         self._n = int(env_num)
         self._obs_dim = int(obs_dim)

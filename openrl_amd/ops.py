@@ -19,6 +19,7 @@ from ._native import (AdamState, BufferPtrs, GatherDesc, NetDesc, PackSrc, PPOHP
 HEAD_VALUE, HEAD_CATEGORICAL, HEAD_GAUSSIAN = nat.ORL_HEAD_VALUE, nat.ORL_HEAD_CATEGORICAL, nat.ORL_HEAD_GAUSSIAN
 ENV_SYNTH, ENV_CARTPOLE, ENV_PENDULUM = nat.ORL_ENV_SYNTH, nat.ORL_ENV_CARTPOLE, nat.ORL_ENV_PENDULUM
 ENV_ACROBOT, ENV_MOUNTAINCAR = nat.ORL_ENV_ACROBOT, nat.ORL_ENV_MOUNTAINCAR
+ENV_MOUNTAINCAR_CONT = nat.ORL_ENV_MOUNTAINCAR_CONT
 N_STATS = nat.ORL_N_STATS
 
 

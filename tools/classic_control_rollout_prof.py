@@ -1,7 +1,9 @@
-"""Fused chain rollouts with the default towers and a Discrete(3) head: Acrobot-v1 (rollout2_kernel<8, 1, 6, 2>) at 4096
+"""Fused chain rollouts with the default towers: Acrobot-v1 (rollout2_kernel<8, 1, 6, 2>) at 4096
 envs x 500 steps next to the synthetic fixed-step env at the same shape (obs 6: rollout2_kernel<8, 1, 0, 0>), and
 MountainCar-v0 (rollout2_kernel<8, 1, 7, 1>) at 4096 x 200 next to the synthetic env at obs 2 (rollout2_kernel<8, 1, 0, 0>
-as well: the synthetic env's Discrete(3) instance takes the observation width at run time).  `--reps` rollouts each after
+as well: the synthetic env's Discrete(3) instance takes the observation width at run time), both with a Discrete(3) head;
+MountainCarContinuous-v0 (rollout2_kernel<2, 2, 8, 1>) at 4096 x 200 next to the synthetic env at obs 2 with the same
+Box(1) Gaussian head (rollout2_kernel<2, 2, 0, 0>).  `--reps` rollouts each after
 one warm-up.  Meant to run under `rocprofv3 --kernel-trace --stats --output-format csv -- python
 tools/classic_control_rollout_prof.py --pair acrobot` (one pair per run, so that the two rows of the kernel statistics are
 the two envs).  Also prints a host-timed ms
@@ -14,10 +16,12 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-PAIRS = {"acrobot": ("Acrobot-v1", 6, 500), "mountaincar": ("MountainCar-v0", 2, 200)}
+PAIRS = {"acrobot": ("Acrobot-v1", 6, 500), "mountaincar": ("MountainCar-v0", 2, 200),
+         "mountaincar_continuous": ("MountainCarContinuous-v0", 2, 200)}
 
 
-def rollouts(env_id, D, N, T, reps, dev="cuda:0"):
+def rollouts(env_id, D, N, T, reps, box=False, dev="cuda:0"):
+    import numpy as np
     import torch
 
     from openrl_amd import spaces
@@ -29,7 +33,8 @@ def rollouts(env_id, D, N, T, reps, dev="cuda:0"):
     from openrl_amd.modules.common import PPONet
 
     cfg = default_cfg(["--seed", "0", "--episode_length", str(T)])
-    kw = {} if not env_id.startswith("Synthetic") else dict(obs_dim=D, episode_limit=T, action_space=spaces.Discrete(3))
+    act = spaces.Box(-1.0, 1.0, (1,), np.float32) if box else spaces.Discrete(3)
+    kw = {} if not env_id.startswith("Synthetic") else dict(obs_dim=D, episode_limit=T, action_space=act)
     env = make(env_id, env_num=N, device=dev, seed=0, **kw)
     net = PPONet(env, cfg=cfg, device=dev, n_rollout_threads=N)
     cfg.num_env_steps = N * T * (reps + 1)
@@ -60,7 +65,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     a = ap.parse_args()
     env_id, D, T = PAIRS[a.pair]
-    out = {e: round(rollouts(e, D, a.envs, T, a.reps), 4) for e in ("SyntheticFixedStep-v0", env_id)}
+    box = a.pair == "mountaincar_continuous"
+    out = {e: round(rollouts(e, D, a.envs, T, a.reps, box), 4) for e in ("SyntheticFixedStep-v0", env_id)}
     print(json.dumps({"ms_per_rollout_host_timed": out, "obs_dim": D, "envs": a.envs, "T": T, "reps": a.reps}))
 
 
